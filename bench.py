@@ -15,7 +15,12 @@ Ranks come from torch.distributed.run (RANK / WORLD_SIZE / LOCAL_RANK / MASTER_*
 `--gpus N` > 1 is given without them, bench.py starts the N rank processes itself before anything
 touches the GPU (fresh child processes, no exec) and relays rank 0's line.
 
-Extra fields: "roofline" (the dominant kernel, per launch from the HIP event pair around the timed
+A plain run (`--gpus 1 --steps K --warmup W`) sets up, settles, warms up, times the K steps and prints
+the result line (metric, value, unit, ms_per_step, ...) -- nothing else.  `--dump-outputs DIR` also
+writes what the last timed step computed (dump_outputs below).  Everything else this file measures or
+checks runs only with `--full`:
+
+Extra fields (--full): "roofline" (the dominant kernel, per launch from the HIP event pair around the timed
 steps on their launch stream -- gaps between launches count; the encode / decode split comes from
 PASS_SPLIT_STEPS untimed steps after the region, whose extra events would perturb it; peak =
 8 TB/s spec, plus a live copy probe; "trace" = the same figure from the committed rocprofv3 kernel
@@ -69,6 +74,13 @@ def parse_args(argv=None):
     ap.add_argument("--stripes", type=int, default=0,
                     help="stripes per GPU (weak) or in total (strong); 0 = the config's")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"])
+    ap.add_argument("--full", action="store_true",
+                    help="also everything beyond the headline figure: kernel form check, roofline, "
+                         "encode / decode split, mixed-pattern decode, copy peak, C5 rebuilds, peer "
+                         "scatter, CPU baseline (the --no-* switches trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs (parity and rebuilt "
+                         "fragments, a fixed sample when large) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-c5", action="store_true", help="skip the C5 rebuild-8 fields")
     ap.add_argument("--no-scatter", action="store_true",
@@ -437,7 +449,7 @@ def rank0_cpu_baseline(co, args, k, m, F, missing):
     """The host-CPU baseline at every N (north_star: "from the same run"): rank 0 times it after
     every GPU measurement of the run, while the other ranks wait on a gloo barrier (blocked in a
     socket read, not spinning on a core).  Returns rank 0's figure (None elsewhere / when off)."""
-    if args.no_cpu_baseline:
+    if args.no_cpu_baseline or not args.full:
         return None
     co.cpu_barrier()  # every rank is done with the GPU
     out = None
@@ -447,6 +459,41 @@ def rank0_cpu_baseline(co, args, k, m, F, missing):
         out["ranks_idle"] = co.world - 1
     co.cpu_barrier()
     return out
+
+
+DUMP_BYTES = 24 << 20  # fragment bytes dumped at most: 12 Mi words, 48 MiB of float32 in all
+DUMP_SEED = 0xD0317
+
+
+def dump_outputs(lay, k, m, missing, outdir):
+    """--dump-outputs: what a caller of the timed path holds after its last step -- the m parity
+    fragments rs_encode wrote and the fragments rs_decode rebuilt -- as outdir/encode_parity.npy
+    (stripes, m, words) and outdir/decode_rebuilt.npy (stripes, len(missing), words): the fragments'
+    little-endian GF(2^16) words as float32 (exact).  The inputs are the splitmix64 fragments of the
+    rank's stripes, the same in every run.  Outputs of more than DUMP_BYTES are sampled, the same way
+    in every run: 16 stripes (the first, the last, seeded others) and of each output fragment three
+    windows (its head, a seeded 4 KiB-aligned offset, its tail)."""
+    import random
+
+    import numpy as np
+
+    S, F = lay.nstripes, lay.blocksize
+    nout = m + len(missing)
+    rng = random.Random(DUMP_SEED)
+    stripes, windows = list(range(S)), [(0, F)]
+    if S * nout * F > DUMP_BYTES:
+        if S > 16:
+            stripes = sorted([0, S - 1] + rng.sample(range(1, S - 1), 14))
+        w = max(4096, DUMP_BYTES // (len(stripes) * nout * 3) // 4096 * 4096)
+        if F > 3 * w:
+            mid = rng.randrange(w // 4096, (F - 2 * w) // 4096 + 1) * 4096
+            windows = [(0, w), (mid, w), ((F - w) // 2 * 2, w)]
+    os.makedirs(outdir, exist_ok=True)
+    for name, frags in (("encode_parity", range(k, k + m)), ("decode_rebuilt", missing)):
+        arr = np.stack([np.stack([np.concatenate(
+            [lay.buf.download(n, s * lay.stripe_stride + f * lay.frag_stride + off) for off, n in windows])
+            for f in frags]) for s in stripes])
+        np.save(os.path.join(outdir, name + ".npy"), arr.view("<u2").astype(np.float32))
 
 
 # ------------------------------------------------------------------ main ----
@@ -518,24 +565,26 @@ def main():
     D.rs_encode(k, m, lay, stream=stream)
     D.rs_decode(k, m, missing, lay, stream=stream)
     stream.synchronize()
-    # which kernel a pass runs, and in how many launches: the run-time compiled bitsliced kernel
-    # (3-4 outputs in one-wave 4 KiB tiles, 5-8 in 16 KiB tiles) counts its launches
-    import ctypes
-    bs_count = _lib.dev().ecamd_bitslice_launches
-    bs_count.restype = ctypes.c_longlong
-    n0 = bs_count()
-    D.rs_encode(k, m, lay, stream=stream)
-    stream.synchronize()
-    bs_enc = bs_count() - n0
-    n0 = bs_count()
-    D.rs_decode(k, m, missing, lay, stream=stream)
-    stream.synchronize()
-    bs_dec = bs_count() - n0
-    # one per-launch figure for both passes only when both run the same form in as many launches
-    if (bs_enc > 0) != (bs_dec > 0) or (bs_enc and bs_enc != bs_dec):
-        raise SystemExit(f"bench.py: encode / decode passes run different kernels or launch counts "
-                         f"(bitsliced launches {bs_enc} / {bs_dec}); the per-launch roofline would be misstated")
-    bs_per_pass = bs_enc
+    bs_per_pass = 0
+    if args.full:
+        # which kernel a pass runs, and in how many launches: the run-time compiled bitsliced kernel
+        # (3-4 outputs in one-wave 4 KiB tiles, 5-8 in 16 KiB tiles) counts its launches
+        import ctypes
+        bs_count = _lib.dev().ecamd_bitslice_launches
+        bs_count.restype = ctypes.c_longlong
+        n0 = bs_count()
+        D.rs_encode(k, m, lay, stream=stream)
+        stream.synchronize()
+        bs_enc = bs_count() - n0
+        n0 = bs_count()
+        D.rs_decode(k, m, missing, lay, stream=stream)
+        stream.synchronize()
+        bs_dec = bs_count() - n0
+        # one per-launch figure for both passes only when both run the same form in as many launches
+        if (bs_enc > 0) != (bs_dec > 0) or (bs_enc and bs_enc != bs_dec):
+            raise SystemExit(f"bench.py: encode / decode passes run different kernels or launch counts "
+                             f"(bitsliced launches {bs_enc} / {bs_dec}); the per-launch roofline would be misstated")
+        bs_per_pass = bs_enc
 
     # The timed steps carry ONE event pair (around all of them): events recorded between the passes
     # are markers the command processor serialises on, and cost ~1% of the value at C3
@@ -574,6 +623,44 @@ def main():
     elapsed = co.reduce([elapsed], op="max")[0]
     co.barrier()
 
+    if args.dump_outputs and rank == 0:  # before anything below writes the buffers again
+        dump_outputs(lay, k, m, missing, args.dump_outputs)
+    value = 2 * total_stripes * k * F * args.steps / GIB / elapsed
+    out = None
+    if rank == 0:
+        out = {
+            "metric": "device-resident encode+decode GiB/s (RS k=10 m=4, 1 MiB frags), 1/2/4/8 GPU"
+            if args.config == "c3" else f"device-resident encode+decode GiB/s ({desc})",
+            "value": round(value, 3),
+            "unit": "GiB/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "settle": {"steps": args.settle, "ms": round(settle_ms, 1),
+                       "note": "untimed steps before the warm-up: the GPU's clocks ramp under sustained load"},
+            "ms_per_step": round(elapsed * 1e3 / args.steps, 4),
+            "higher_is_better": True,
+            "scaling": args.scaling,
+            "vs_baseline": None,
+            "dtype": "u16 (GF(2^16) words)",
+            "data": "synthetic (splitmix64 fragments generated in HBM)",
+            "config": {"workload": desc, "k": k, "m": m, "fragment_bytes": F,
+                       "stripes_per_gpu": S, "stripes_total": total_stripes,
+                       "decode_missing": missing,
+                       "parallelism": f"stripe-sharded x{world} (no data-path collective)"},
+            "ranks_seen": ranks_seen,
+            "coord_backend": co.coord_backend,
+            "devices": co.devices,
+            "shared_devices": co.shared_devices,
+        }
+    if not args.full:  # the plain run ends here: the headline figure and nothing else
+        lay.buf.free()
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        co.barrier()
+        co.close()
+        return
+
     region_ms = ev_all[0].elapsed_ms(ev_all[1])
     # encode / decode split: PASS_SPLIT_STEPS more steps with an event between the passes (untimed)
     ev = [(D.Event(), D.Event(), D.Event()) for _ in range(PASS_SPLIT_STEPS)]
@@ -587,7 +674,6 @@ def main():
     enc_ms = [a.elapsed_ms(b) for a, b, _ in ev]
     dec_ms = [b.elapsed_ms(c) for _, b, c in ev]
     obj_bytes = S * k * F  # object bytes per batch on this rank
-    value = 2 * total_stripes * k * F * args.steps / GIB / elapsed
     enc_gibs = obj_bytes / GIB / (sum(enc_ms) / len(enc_ms) / 1e3)
     dec_gibs = obj_bytes / GIB / (sum(dec_ms) / len(dec_ms) / 1e3)
     per_rank = co.reduce([enc_gibs if r == rank else 0.0 for r in range(world)] +
@@ -629,7 +715,6 @@ def main():
         per_rank_mixed = co.reduce([mixed_gibs if r == rank else 0.0 for r in range(world)], "sum")
     co.barrier()
 
-    out = None
     if rank == 0:
         copy_gbs, copy_probes = measured_copy_peak(D, stream)
         summ, summ_src = profile_summary(args.config)
@@ -656,27 +741,7 @@ def main():
                      "frac": round(t_algo / timed_ns / HBM_PEAK_GBS, 4),
                      "kernel_ms_per_step": round(2 * t_pass * timed_ns / 1e6, 4),
                      "profiled_ms_per_step": (summ or {}).get("ms_per_step")}
-        out = {
-            "metric": "device-resident encode+decode GiB/s (RS k=10 m=4, 1 MiB frags), 1/2/4/8 GPU"
-            if args.config == "c3" else f"device-resident encode+decode GiB/s ({desc})",
-            "value": round(value, 3),
-            "unit": "GiB/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "settle": {"steps": args.settle, "ms": round(settle_ms, 1),
-                       "note": "untimed steps before the warm-up: the GPU's clocks ramp under sustained load"},
-            "ms_per_step": round(elapsed * 1e3 / args.steps, 4),
-            "higher_is_better": True,
-            "scaling": args.scaling,
-            "vs_baseline": None,
-            "dtype": "u16 (GF(2^16) words)",
-            "data": "synthetic (splitmix64 fragments generated in HBM)",
-            "config": {"workload": desc, "k": k, "m": m, "fragment_bytes": F,
-                       "stripes_per_gpu": S, "stripes_total": total_stripes,
-                       "decode_missing": missing,
-                       "parallelism": f"stripe-sharded x{world} (no data-path collective)"},
-            "ranks_seen": ranks_seen,
+        out.update({
             "per_rank_encode_gibs": [round(x, 2) for x in per_rank[:world]],
             "per_rank_decode_gibs": [round(x, 2) for x in per_rank[world:]],
             "encode_gibs_per_gpu": round(enc_gibs, 3),
@@ -686,9 +751,6 @@ def main():
                                           if per_rank_mixed else None),
             "per_rank_decode_mixed_gibs": ([round(x, 2) for x in per_rank_mixed]
                                            if per_rank_mixed else None),
-            "coord_backend": co.coord_backend,
-            "devices": co.devices,
-            "shared_devices": co.shared_devices,
             "roofline": {"bound": "hbm", "kernel": kernel, "kernel_form": kernel_form,
                          "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
@@ -711,7 +773,7 @@ def main():
                          "frac_of_measured_copy": round(achieved / copy_gbs, 4),
                          "algorithmic_bytes_per_launch": algo_bytes,
                          "trace": trace},
-        }
+        })
     lay.buf.free()
     # C5 (BASELINE configs[4]) on every rank at once, after one barrier: each GPU rebuilds its own
     # 32 stripes under the same concurrent load as the timed steps

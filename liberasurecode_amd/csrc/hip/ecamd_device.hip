@@ -3130,6 +3130,11 @@ int ecamd_small_server_wait(const uint32_t* flag, uint32_t value)
             const hipError_t q = hipStreamQuery(sv->st);
             if (q == hipSuccess) {  // the server exited before this request: run it again, request pending
                 if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) == value) return 0;
+                // Its workgroups leave one by one (each idle_ticks after its own last poll), so some of this
+                // request's may have run and counted while the others were gone: the self-resetting done and
+                // checksum counters then start the rerun above 0, a workgroup takes itself for the last one
+                // early, and the flag (and the checksums) go out before every output.  Zero them first.
+                HIP_TRY(hipMemsetAsync(sv->scratch, 0, (64 + 16) * 4, sv->st));
                 const int rc = server_launch(sv, sv->key, sv->prev, true);
                 if (rc) return rc;
                 sv->last = now;

@@ -27,7 +27,7 @@ def run_bench(*args, env=None):
                                                     (2, "strong", [1024, 1024]),
                                                     (3, "strong", [683, 683, 682])])
 def test_launcher_starts_ranks_and_covers_every_stripe(gpus, scaling, per_rank):
-    r = run_bench("--gpus", str(gpus), "--dry-run", "--scaling", scaling, "--cpu-seconds", "0.2")
+    r = run_bench("--gpus", str(gpus), "--dry-run", "--full", "--scaling", scaling, "--cpu-seconds", "0.2")
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
     assert line["dry_run"] and line["covered_once"]
@@ -43,9 +43,11 @@ def test_launcher_starts_ranks_and_covers_every_stripe(gpus, scaling, per_rank):
 
 
 def test_dry_run_without_cpu_baseline():
-    r = run_bench("--gpus", "2", "--dry-run", "--no-cpu-baseline")
-    assert r.returncode == 0, r.stderr[-2000:]
-    assert "cpu_baseline" not in json.loads(r.stdout.strip().splitlines()[-1])
+    # the CPU baseline is part of --full, and --no-cpu-baseline takes it out again; a plain run has none
+    for extra in (["--full", "--no-cpu-baseline"], []):
+        r = run_bench("--gpus", "2", "--dry-run", *extra)
+        assert r.returncode == 0, r.stderr[-2000:]
+        assert "cpu_baseline" not in json.loads(r.stdout.strip().splitlines()[-1])
 
 
 def test_mismatched_world_fails_loudly():
@@ -55,7 +57,7 @@ def test_mismatched_world_fails_loudly():
 
 
 def test_single_rank_dry_run():
-    r = run_bench("--dry-run", "--cpu-seconds", "0.2")
+    r = run_bench("--dry-run", "--full", "--cpu-seconds", "0.2")
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
     assert line["n_gpus"] == 1 and line["stripes_per_rank"] == [256]

@@ -364,6 +364,35 @@ def test_decode_direct_matches_general_path():
     assert sum(1 for _, rc, _, ok in res["11"] if ok) > 100
 
 
+def test_percall_crc_across_server_exit():
+    """The resident small server's workgroups leave one by one around its idle time (2000 us, or
+    ECAMD_PERCALL_SERVER_IDLE_US): a call posted just then is taken by some of them only, and the server
+    is started again with the request pending (ecamd_small_server_wait).  Calls of a size of several
+    workgroups with a fused checksum, the pause between them swept across the idle time, must all give
+    the expected fragments (the rerun once started from the first run's counts: checksums and the
+    completion flag went out before every workgroup was done)."""
+    import time
+    import torch  # noqa: F401  (one HIP runtime per process: torch's)
+    k, m = 10, 4
+    idle_us = min(max(int(os.environ.get("ECAMD_PERCALL_SERVER_IDLE_US", "2000")), 50), 1000000)
+    desc = E.create(E.EC_BACKEND_LIBERASURECODE_RS_VAND, k, m, hd=m, ct=E.CHKSUM_CRC32)
+    datas = [payload_bytes(65536 + 3, s) for s in (1, 2)]
+    wants = [rs_expected(k, m, d, E.CHKSUM_CRC32) for d in datas]
+    bad = []
+    for n, gap_us in enumerate(range(idle_us - 100, idle_us + 300, 2)):
+        rc, dp, pp, flen = E.encode(desc, datas[n & 1])
+        t0 = time.perf_counter()
+        assert rc == 0
+        frags = E.fragments(dp, k, flen) + E.fragments(pp, m, flen)
+        E.lib().liberasurecode_encode_cleanup(desc, dp, pp)
+        if frags != wants[n & 1]:
+            bad.append((gap_us, [j for j in range(k + m) if frags[j] != wants[n & 1][j]]))
+        while (time.perf_counter() - t0) * 1e6 < gap_us:
+            pass
+    E.lib().liberasurecode_instance_destroy(desc)
+    assert not bad, bad[:5]
+
+
 @pytest.mark.parametrize("legacy", [False, True])
 @pytest.mark.parametrize("km", [(10, 4), (4, 2), (20, 8), (10, 6, 4), (3, 3, 3)])
 def test_percall_crc_fused(monkeypatch, km, legacy):

@@ -1,6 +1,7 @@
 #!/bin/bash
 # rocprofv3 evidence for the bench line: kernel trace + separate PMC passes of EXACTLY the driver's
-# command (python3 bench.py --gpus 1 --steps 20 --warmup 5), then tools/summarize_prof.py picks
+# command (python3 bench.py --gpus 1 --steps 20 --warmup 5) with --full, whose launch sequence
+# tools/summarize_prof.py --pre 4 indexes (a plain run launches 2 before the settle steps), which then picks
 # the timed launches of the dominant kernel.  Usage: tools/gpu_prof.sh [round] [cfg]
 set -o pipefail
 R="${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}"
@@ -8,7 +9,7 @@ cd "$R"; mkdir -p gpurun_out
 export TMPDIR=/tmp
 RND="${1:-r02}"
 CFG="${2:-c3}"
-B="python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 --config $CFG"
+B="python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 --config $CFG --full"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$R/gpurun_out/prof_trace_$CFG" -o run --output-format csv -- $B > gpurun_out/prof_trace_$CFG.log 2>&1 || { echo "TRACE FAILED rc=$?"; tail -20 gpurun_out/prof_trace_$CFG.log; exit 1; }
 grep '^{' gpurun_out/prof_trace_$CFG.log | tail -1 > gpurun_out/bench_prof_$CFG.json
 timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d "$R/gpurun_out/prof_fetch_$CFG" -o run --output-format csv -- $B --no-cpu-baseline > gpurun_out/prof_fetch_$CFG.log 2>&1 || { echo "FETCH FAILED rc=$?"; tail -20 gpurun_out/prof_fetch_$CFG.log; exit 1; }
