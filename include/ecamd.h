@@ -186,6 +186,41 @@ int ecamd_rs_reconstruct(int k, int m, const int *missing, int dest, void *base,
                          int64_t stripe_stride, int64_t frag_stride, int64_t blocksize,
                          int nstripes, void *stream);
 
+/* ---- stripe consistency check: do the fragments of a stripe still agree with each other? ----
+ * Consistency of S stripes in place.  The first k fragments not in the -1 terminated `missing`
+ * (NULL or empty: none) are the inputs, as in ecamd_rs_decode; every OTHER available fragment f is
+ * "checked": d_status[s] gets bit f when any of its `blocksize` bytes differs from the value the
+ * inputs imply.  Bits of inputs and of missing fragments are never set.  d_status (nstripes
+ * uint32, device memory) is overwritten.  *checked (host, may be NULL) receives the mask of checked
+ * fragments.  Nothing else is written; asynchronous on stream.
+ * ECAMD_EINVAL: more than m missing, k+m > 32 (d_status is then untouched).  With exactly m missing
+ * nothing is checked: status all zero, *checked 0.
+ * Layout rules as for the other strided calls (16-byte aligned base and strides, any blocksize >= 1);
+ * exactly `blocksize` bytes of each fragment are compared, bytes between blocksize and frag_stride
+ * never influence the status.  Framed fragments (ecamd_frame_encode) are checked by passing
+ * d_frags + 80 as `base`: the payload follows the 80-byte header, and 80 is a multiple of 16.
+ * Reading the status: a single parity bit -- that parity fragment is bad; all checked bits -- an input
+ * (or several fragments) is bad; re-check with a suspect listed as missing to isolate it.
+ * Whole bitsliced tiles run one read-only fused kernel (the codec's XOR network over the K inputs and
+ * the checked fragments; a consistent stripe causes no write); tails, small fragments, shapes the
+ * bitsliced form declines, maps still compiling (knob "bitslice" 1) and knob "bitslice" 0 compute the
+ * expected fragments into library-owned scratch of at most 64 MiB per (device, stream), stripe chunk
+ * by stripe chunk, and compare (DESIGN.md "Consistency check"). */
+int ecamd_rs_check(int k, int m, const int *missing, const void *base, int64_t stripe_stride,
+                   int64_t frag_stride, int64_t blocksize, int nstripes, uint32_t *d_status,
+                   uint32_t *checked, void *stream);
+/* flat_xor_hd, all k+m fragments present: bit k+p when stored parity p differs from the XOR its
+ * parity bitmap names (xor_code_encode).  Same layout rules; ECAMD_EINVAL (d_status untouched) when
+ * (k, m, hd) is not a code init_xor_hd_code accepts. */
+int ecamd_xor_check(int k, int m, int hd, const void *base, int64_t stripe_stride,
+                    int64_t frag_stride, int64_t blocksize, int nstripes, uint32_t *d_status,
+                    void *stream);
+/* Fused check launches enqueued by this process (tests pin which path ran). */
+long long ecamd_check_fused_launches(void);
+/* Build time, as ecamd_bitslice_prebuild: the fused check kernel(s) of (k, m, missing).  Returns the
+ * number of code objects present (0: the check takes no bitsliced form), < 0 on error. */
+int ecamd_check_prebuild(int k, int m, const int *missing, const char *arch, const char *dir);
+
 /* ---- flat_xor_hd on strided batches: the reference's xor_code_encode,
  * xor_hd_decode (decode_parity as its argument) and xor_reconstruct_one
  * (src/builtin/xor_codes/xor_code.c:180-314, xor_hd_code.c:574-662) replayed exactly per erasure

@@ -13,6 +13,8 @@
  *   ecamd_rs_decode_map               coefficient rows of liberasurecode_rs_vand_decode
  *                                     (liberasurecode_rs_vand.c:426-481); missing parity is
  *                                     expressed directly over the first k available fragments
+ *   ecamd_rs_check_map                the same algebra for every surviving fragment beyond the first
+ *                                     k: what the inputs imply it holds (no reference counterpart)
  *   ecamd_rs_reconstruct_map          coefficient row of liberasurecode_rs_vand_reconstruct
  *                                     (liberasurecode_rs_vand.c:483-558)
  */
@@ -43,6 +45,15 @@ int ecamd_rs_decode_map(const int *G, int k, int m, const int *missing, int rebu
 /* Reconstruct map for one destination: inputs[*ninputs] and coeff[*ninputs]. */
 int ecamd_rs_reconstruct_map(const int *G, int k, int m, const int *missing, int dest, int *inputs,
                              int *ninputs, int *coeff);
+
+/* Check map (ecamd_rs_check, ecamd.h) for a -1 terminated missing list (NULL: none).
+ * inputs[k]: first k available; checked[*ncheck]: the other available fragments, ascending;
+ * coeff[*ncheck * k]: row i gives fragment checked[i] over the inputs.  With nothing missing the
+ * rows are the generator's parity rows (the encode map); otherwise row f is G[f] * inv(G[inputs]),
+ * the algebra ecamd_rs_decode_map uses for missing parity.  -1 if more than m missing; exactly m
+ * missing leaves *ncheck 0. */
+int ecamd_rs_check_map(const int *G, int k, int m, const int *missing, int *inputs, int *checked,
+                       int *coeff, int *ncheck);
 
 /* LDS split-table image for rows [row0,row0+width) x inputs [col0,col0+ncols) of the R x K
  * matrix coeff; width in {2,4,8}.  Returns the byte count written (ncols*512*width*2). */

@@ -25,6 +25,7 @@
 #include "../host/gf16.hpp"
 #include "../host/tables.hpp"
 #include "ecamd.h"
+#include "ecamd_host.h"
 #include "ecamd_internal.hpp"
 #include "ecamd_kernels.hpp"
 #include "ecamd_frame.hpp"
@@ -392,6 +393,8 @@ struct Tuning {
     Knob bs_tile_threads{256};    //   ecamd_bs_kernel, plain 5-8-output maps: lanes per workgroup (128 / 256 / 512:
                                   //   8 / 16 / 32 KiB tiles)
     Knob bs_tile_per_cu{0};       //   ecamd_bs_kernel in 16 KiB tiles (5-8 outputs)
+    Knob check_per_cu{-1};        //   the check form in one-wave tiles (ecamd_rs_check; < 0: as bs_wave_per_cu's policy,
+                                  //   by the K + R fragments a tile reads; DESIGN.md "Consistency check")
     Knob frame_crc_per_cu{0};     //   the bitsliced crc variant (framed CRC32 encode)
     Knob bs_plain_prefetch{0};    //   one-wave plain maps: chunks (0 / 2 / 4) of the next input loaded before each network
     Knob frame_copy_per_cu{0};    //   framed split / join streaming kernels (copy_lds, ecamd_frame_api.hip)
@@ -511,10 +514,10 @@ namespace ecamd {
 hipFunction_t bitslice_function(int dev, const std::vector<int>& coeff, int R, int K, int depth, bool wait,
                                 std::shared_ptr<void>& hold, bool copy = false, int crc = 0, bool wave = false,
                                 const std::vector<int>* in_shift = nullptr, int prefetch = 0, int* status = nullptr,
-                                const BsOcc* occ = nullptr);
+                                const BsOcc* occ = nullptr, bool check = false);
 int bitslice_prebuild(const std::vector<int>& coeff, int R, int K, int depth, bool copy, int crc, bool wave,
                       const std::vector<int>* in_shift, int prefetch, const BsOcc& occ, const std::string& arch,
-                      const std::string& dir);
+                      const std::string& dir, bool check = false);
 int bitslice_launch(hipFunction_t fn, const BsArgs& args, int grid, hipStream_t st,
                     const std::shared_ptr<void>& hold, int threads = 256, unsigned lds = 0);
 }  // namespace ecamd
@@ -1343,9 +1346,18 @@ bool bs_form(int nrows, int K, bool copy, bool unaligned, BsForm& f)
 // Lanes per workgroup and bytes of each fragment per tile of a form.
 int bs_threads(const BsForm& f) { return f.wave ? 64 : f.occ.threads ? f.occ.threads : 256; }
 
+// chk (ecamd_rs_check): the map is a syndrome matrix [A | I] whose last nrows inputs are the stored
+// fragments under test; the check form of the kernel writes no fragment (out_off unused) and ORs
+// bit chk->bits[r] into chk->status[stripe] for every row r whose syndrome is not zero.
+struct BsCheck {
+    uint32_t* status;
+    const uint8_t* bits;
+};
+std::atomic<long long> g_check_fused{0};  // check-form launches enqueued by this process
+
 int64_t launch_bitslice(const ecamd_map* map, int row0, int nrows, const ApplyArgs& base,
                         const int64_t* in_off, const int64_t* out_off, int64_t bs, int nstripes,
-                        hipStream_t st, int* rc, const int64_t* copy_off = nullptr)
+                        hipStream_t st, int* rc, const int64_t* copy_off = nullptr, const BsCheck* chk = nullptr)
 {
     *rc = 0;
     const int mode = g_tune.bitslice;
@@ -1357,9 +1369,9 @@ int64_t launch_bitslice(const ecamd_map* map, int row0, int nrows, const ApplyAr
     if (!bs_form(nrows, K, copy_off != nullptr, unaligned, form)) return 0;
     ApplyArgs a = base;
     a.ncols = K;
-    a.nrows = nrows;
+    a.nrows = chk ? 0 : nrows;
     for (int j = 0; j < K; j++) a.in_off[j] = in_off[j];
-    for (int r = 0; r < nrows; r++) a.out_off[r] = out_off[row0 + r];
+    for (int r = 0; r < a.nrows; r++) a.out_off[r] = out_off[row0 + r];
     const bool wave = form.wave;
     const int threads = bs_threads(form);
     const int64_t tile = static_cast<int64_t>(threads) * 64;  // kBsTileWave / kBsTile at 64 / 256 lanes
@@ -1379,7 +1391,7 @@ int64_t launch_bitslice(const ecamd_map* map, int row0, int nrows, const ApplyAr
     std::vector<int> shifts;
     const uint32_t in_records = realign_records(a, K, cover, copy_off != nullptr, shifts);
     hipFunction_t fn = bitslice_function(map->device, sub, nrows, K, form.depth, mode == 2, hold, copy_off != nullptr,
-                                         0, wave, &shifts, form.prefetch, nullptr, &form.occ);
+                                         0, wave, &shifts, form.prefetch, nullptr, &form.occ, chk != nullptr);
     if (!fn) return 0;
     BsArgs b{};
     b.in_base = a.in_base;
@@ -1392,7 +1404,11 @@ int64_t launch_bitslice(const ecamd_map* map, int row0, int nrows, const ApplyAr
     b.tiles_per_stripe = static_cast<uint32_t>(cover / tile);
     b.ntiles = b.tiles_per_stripe * static_cast<uint32_t>(nstripes);
     for (int j = 0; j < K; j++) b.in_off[j] = a.in_off32[j];
-    for (int r = 0; r < nrows; r++) b.out_off[r] = a.out_off32[r];
+    for (int r = 0; r < a.nrows; r++) b.out_off[r] = a.out_off32[r];
+    if (chk) {
+        b.status = chk->status;
+        for (int r = 0; r < nrows; r++) b.status_bit[r] = chk->bits[row0 + r];
+    }
     if (copy_off) {  // offsets as idx * step (the kernel keeps 8 scalar registers, not 32)
         int64_t step = 0;
         for (int j = 0; j < K; j++)
@@ -1432,6 +1448,7 @@ int64_t launch_bitslice(const ecamd_map* map, int row0, int nrows, const ApplyAr
             c.in_base = b.in_base + s0 * b.in_stride;
             c.out_base = b.out_base + s0 * b.out_stride;
             if (c.copy_records) c.copy_base = b.copy_base + s0 * b.copy_stride;
+            if (chk) c.status = b.status + s0;  // the kernel indexes it by the launch's own stripe number
         }
         c.ntiles = b.tiles_per_stripe * static_cast<uint32_t>(n);
         // bs_grid 1: one workgroup per tile (the dispatcher balances the tiles); 0: the resident slots
@@ -1439,13 +1456,16 @@ int64_t launch_bitslice(const ecamd_map* map, int row0, int nrows, const ApplyAr
         // resident workgroups per CU: one-wave plain maps bs_wave_per_cu; copy-through maps bs_copy_per_cu
         // when every input is read aligned (C3 objects, decode-joins), bs_copy_realign_per_cu when inputs
         // are realigned in registers (Swift's segments); 16 KiB tiles bs_tile_per_cu
+        // (the check form reads its K fragments, checked ones included, and writes none: knob check_per_cu)
         const int wg_cap = !wave ? static_cast<int>(g_tune.bs_tile_per_cu)
+                        : chk ? (g_tune.check_per_cu >= 0 ? static_cast<int>(g_tune.check_per_cu) : K >= 20 ? 0 : 7)
                         : !copy_off ? (g_tune.bs_wave_per_cu >= 0 ? static_cast<int>(g_tune.bs_wave_per_cu)
                                                                    : K + nrows >= 20 ? 0 : 7)
                         : shifts.empty() ? static_cast<int>(g_tune.bs_copy_per_cu)
                                          : static_cast<int>(g_tune.bs_copy_realign_per_cu);
         const unsigned lds = cap_lds(fn, wg_cap);
         *rc = bitslice_launch(fn, c, static_cast<int>(grid), st, hold, threads, lds);
+        if (chk && *rc == 0) g_check_fused.fetch_add(1, std::memory_order_relaxed);
     }
     return *rc ? 0 : cover;
 }
@@ -1773,6 +1793,9 @@ int rs_entry(int kind, int k, int m, const int* missing, int rebuild, int dest,
         fm = rs_encode_map(G, k, m);
     else if (kind == 1) {
         if (rs_decode_map(G, k, m, miss, rebuild != 0, fm) != 0)
+            return fail(ECAMD_EINVAL, "too many missing fragments (%zu > m=%d)", miss.size(), m);
+    } else if (kind == 4) {  // ecamd_rs_check: every surviving fragment beyond the first k
+        if (rs_check_map(G, k, m, miss, fm) != 0)
             return fail(ECAMD_EINVAL, "too many missing fragments (%zu > m=%d)", miss.size(), m);
     } else {
         if (rs_reconstruct_map(G, k, m, miss, dest, fm) != 0)
@@ -2852,6 +2875,8 @@ int ecamd_tune(const char* key, int value)
         g_tune.frame_copy_per_cu = value < 0 ? 0 : std::min(value, 32);
     } else if (k == "bs_tile_threads") {
         g_tune.bs_tile_threads = value == 128 || value == 512 ? value : 256;
+    } else if (k == "check_per_cu") {
+        g_tune.check_per_cu = value < 0 ? -1 : std::min(value, 32);  // < 0: by shape
     } else if (k == "bs_tile_per_cu") {
         g_tune.bs_tile_per_cu = value < 0 ? 0 : std::min(value, 32);
     } else if (k == "frame_crc_per_cu") {
@@ -3786,6 +3811,254 @@ int ecamd_event_elapsed_ms(void* start, void* stop, float* ms)
     HIP_TRY(hipEventSynchronize(static_cast<hipEvent_t>(stop)));
     HIP_TRY(hipEventElapsedTime(ms, static_cast<hipEvent_t>(start), static_cast<hipEvent_t>(stop)));
     return 0;
+}
+
+}  // extern "C"
+
+// ---- stripe consistency check (ecamd_rs_check / ecamd_xor_check, DESIGN.md "Consistency check") ----
+//
+// Fused path (rs_vand, whole bitsliced tiles): the check form of the bitsliced kernel over the
+// syndrome map [A | I] reads the K inputs and the R checked fragments and writes only the status bits
+// of inconsistent stripes.  Generic path (everything else: tails, small fragments, shapes bs_form
+// declines, maps still compiling, knob bitslice 0, flat XOR): the existing kernels compute the
+// expected fragments into the stream context's scratch (slot kCheckScratchSlot, at most
+// kCheckScratchBytes, so long batches go stripe chunk by stripe chunk and long fragments byte range
+// by byte range) and check_compare_kernel compares them with the stored ones.  Both OR into the same
+// status words, which ecamd_*_check clears first.
+namespace {
+
+struct CheckCmpArgs {
+    const uint8_t* base;  // stored: row r of stripe s at base + s*stripe_stride + off[r]
+    const uint8_t* calc;  // computed: row r of stripe s at calc + (s*nrows + r)*pitch
+    uint32_t* status;     // of the launch's first stripe
+    int64_t stripe_stride;
+    int64_t pitch;
+    int64_t len;          // bytes compared per fragment
+    int64_t off[32];
+    uint8_t bit[32];
+    int nrows;
+};
+
+// grid (x, row, stripe): 16-byte pieces of exactly `len` bytes, the last piece masked to the
+// fragment's own bytes (read byte by byte, so nothing past `len` is ever touched); one atomicOr per
+// (wave, row) that differs, none for a wave that sees no difference.
+__global__ void __launch_bounds__(256) check_compare_kernel(CheckCmpArgs a)
+{
+    const int r = blockIdx.y;
+    const int64_t s = blockIdx.z;
+    const uint8_t* x = a.base + s * a.stripe_stride + a.off[r];
+    const uint8_t* y = a.calc + (s * a.nrows + r) * a.pitch;
+    const int64_t whole = a.len >> 4;
+    uint32_t d = 0;
+    for (int64_t p = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x; p < whole;
+         p += static_cast<int64_t>(gridDim.x) * 256) {
+        const uint4 u = *reinterpret_cast<const uint4*>(x + p * 16);
+        const uint4 v = *reinterpret_cast<const uint4*>(y + p * 16);
+        d |= (u.x ^ v.x) | (u.y ^ v.y) | (u.z ^ v.z) | (u.w ^ v.w);
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+        for (int64_t i = whole << 4; i < a.len; i++) d |= static_cast<uint32_t>(x[i] ^ y[i]);
+    if (__ballot(d != 0u) != 0ull && (threadIdx.x & 63u) == 0u) atomicOr(a.status + s, 1u << a.bit[r]);
+}
+
+// Bytes [from, bs) of the nrows fragments at off[] (bit bits[r] each) of every stripe against what
+// apply(f0, len, s0, ns, calc, pitch) computes for bytes [f0, f0 + len) of stripes [s0, s0 + ns).
+// `from` a multiple of 16.
+template <class Apply>
+int check_generic(int dev, void* stream, const uint8_t* base, int64_t stripe_stride, const int64_t* off,
+                  const uint8_t* bits, int nrows, int64_t from, int64_t bs, int nstripes, uint32_t* d_status,
+                  Apply&& apply)
+{
+    if (from >= bs || nrows <= 0 || nstripes <= 0) return 0;
+    if (nrows > 32) return fail(ECAMD_EINVAL, "check of %d fragments", nrows);
+    const int64_t cap = static_cast<int64_t>(kCheckScratchBytes);
+    const int64_t seg = std::max<int64_t>(65536, cap / nrows / 65536 * 65536);  // fragment bytes per pass
+    for (int64_t f0 = from; f0 < bs; f0 += seg) {
+        const int64_t len = std::min(seg, bs - f0);
+        const int64_t pitch = (len + 255) & ~int64_t(255);
+        const int per = static_cast<int>(std::min<int64_t>(std::clamp<int64_t>(cap / (pitch * nrows), 1, 65535), nstripes));
+        uint32_t* scratch = nullptr;
+        int rc = stream_scratch(dev, stream, kCheckScratchSlot, static_cast<size_t>(per) * nrows * pitch / 4, &scratch);
+        if (rc) return rc;
+        auto* calc = reinterpret_cast<uint8_t*>(scratch);
+        for (int s0 = 0; s0 < nstripes; s0 += per) {
+            const int ns = std::min(per, nstripes - s0);
+            if ((rc = apply(f0, len, s0, ns, calc, pitch))) return rc;
+            CheckCmpArgs c{};
+            c.base = base + s0 * stripe_stride + f0;
+            c.calc = calc;
+            c.status = d_status + s0;
+            c.stripe_stride = stripe_stride;
+            c.pitch = pitch;
+            c.len = len;
+            c.nrows = nrows;
+            for (int r = 0; r < nrows; r++) {
+                c.off[r] = off[r];
+                c.bit[r] = bits[r];
+            }
+            const unsigned gx = static_cast<unsigned>(std::clamp<int64_t>(((len >> 4) + 1023) / 1024, 1, 1024));
+            hipLaunchKernelGGL(check_compare_kernel, dim3(gx, static_cast<unsigned>(nrows), static_cast<unsigned>(ns)),
+                               dim3(256), 0, static_cast<hipStream_t>(stream), c);
+            HIP_TRY(hipGetLastError());
+        }
+    }
+    return 0;
+}
+
+int check_layout(const void* base, int64_t stripe_stride, int64_t frag_stride, int64_t blocksize, int nstripes,
+                 const uint32_t* d_status)
+{
+    if (!base || !d_status || nstripes < 0 || blocksize < 1 || frag_stride < blocksize)
+        return fail(ECAMD_EINVAL, "bad base / status / blocksize / strides");
+    if (!aligned16(base) || stripe_stride % 16 || frag_stride % 16)
+        return fail(ECAMD_EINVAL, "fragment addresses must be 16-byte aligned");
+    return 0;
+}
+
+// Rows [row0, row0 + nrows) of a check map as the syndrome matrix [A | I] over its K inputs followed
+// by those rows' own fragments.
+std::vector<int> syndrome_rows(const std::vector<int>& coeff, int K, int row0, int nrows)
+{
+    const int W = K + nrows;
+    std::vector<int> syn(static_cast<size_t>(nrows) * W, 0);
+    for (int r = 0; r < nrows; r++) {
+        for (int j = 0; j < K; j++) syn[static_cast<size_t>(r) * W + j] = coeff[static_cast<size_t>(row0 + r) * K + j];
+        syn[static_cast<size_t>(r) * W + K + r] = 1;
+    }
+    return syn;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ecamd_rs_check(int k, int m, const int* missing, const void* base, int64_t stripe_stride, int64_t frag_stride,
+                   int64_t blocksize, int nstripes, uint32_t* d_status, uint32_t* checked, void* stream)
+{
+    int dev = 0;
+    int rc = ensure_device(&dev);
+    if (rc) return rc;
+    if (k <= 0 || m < 0 || k + m > 32) return fail(ECAMD_EINVAL, "check needs k + m <= 32 (k=%d m=%d)", k, m);
+    if ((rc = check_layout(base, stripe_stride, frag_stride, blocksize, nstripes, d_status))) return rc;
+    std::shared_ptr<RsEntry> e;
+    if ((rc = rs_entry(4, k, m, missing, 0, -1, e))) return rc;
+    const int K = static_cast<int>(e->inputs.size()), R = static_cast<int>(e->outputs.size());
+    uint32_t mask = 0;
+    for (int f : e->outputs) mask |= 1u << f;
+    if (checked) *checked = mask;
+    if (nstripes == 0) return 0;
+    const StreamUse use(dev, stream);  // the scratch of its stream context outlives this call
+    const auto st = static_cast<hipStream_t>(stream);
+    HIP_TRY(hipMemsetAsync(d_status, 0, static_cast<size_t>(nstripes) * sizeof(uint32_t), st));
+    if (R == 0) return 0;
+    const auto* b = static_cast<const uint8_t*>(base);
+    std::vector<int64_t> in_off, chk_off;
+    std::vector<uint8_t> bits;
+    for (int i : e->inputs) in_off.push_back(i * frag_stride);
+    for (int f : e->outputs) {
+        chk_off.push_back(f * frag_stride);
+        bits.push_back(static_cast<uint8_t>(f));
+    }
+    // whole tiles through the fused kernel, one launch per group of 8 rows; what every group covered
+    // is done, the rest of each fragment goes the generic way
+    int64_t cover = blocksize;
+    for (int row0 = 0; row0 < R; row0 += 8) {
+        const int nrows = std::min(8, R - row0);
+        int64_t done = 0;
+        if (K + nrows <= kBsMaxK) {
+            ecamd_map syn;
+            syn.device = dev;
+            syn.R = nrows;
+            syn.K = K + nrows;
+            syn.coeff = syndrome_rows(e->map->coeff, K, row0, nrows);
+            std::vector<int64_t> off(in_off);
+            off.insert(off.end(), chk_off.begin() + row0, chk_off.begin() + row0 + nrows);
+            ApplyArgs a{};
+            a.in_base = b;
+            a.in_stride = stripe_stride;
+            const BsCheck chk{d_status, bits.data() + row0};
+            int brc = 0;
+            done = launch_bitslice(&syn, 0, nrows, a, off.data(), nullptr, blocksize, nstripes, st, &brc, nullptr, &chk);
+            if (brc) return brc;
+        }
+        cover = std::min(cover, done);
+    }
+    return check_generic(dev, stream, b, stripe_stride, chk_off.data(), bits.data(), R, cover, blocksize, nstripes,
+                         d_status, [&](int64_t f0, int64_t len, int s0, int ns, uint8_t* calc, int64_t pitch) {
+                             ApplyArgs a{};
+                             a.in_base = b + s0 * stripe_stride;
+                             a.in_stride = stripe_stride;
+                             a.out_base = calc;
+                             a.out_stride = R * pitch;
+                             std::vector<int64_t> io(in_off), oo;
+                             for (auto& v : io) v += f0;
+                             for (int r = 0; r < R; r++) oo.push_back(r * pitch);
+                             return launch_gf16<false>(e->map.get(), a, io.data(), oo.data(), len, ns, st);
+                         });
+}
+
+int ecamd_xor_check(int k, int m, int hd, const void* base, int64_t stripe_stride, int64_t frag_stride,
+                    int64_t blocksize, int nstripes, uint32_t* d_status, void* stream)
+{
+    int dev = 0;
+    int rc = ensure_device(&dev);
+    if (rc) return rc;
+    unsigned pb[32], db[32];
+    if (k <= 0 || m <= 0 || k + m > 32 || ecamd_xor_code_tables(k, m, hd, pb, db) != 0)
+        return fail(ECAMD_EINVAL, "not a flat_xor_hd code: k=%d m=%d hd=%d", k, m, hd);
+    if ((rc = check_layout(base, stripe_stride, frag_stride, blocksize, nstripes, d_status))) return rc;
+    if (nstripes == 0) return 0;
+    const StreamUse use(dev, stream);
+    const auto st = static_cast<hipStream_t>(stream);
+    HIP_TRY(hipMemsetAsync(d_status, 0, static_cast<size_t>(nstripes) * sizeof(uint32_t), st));
+    const auto* b = static_cast<const uint8_t*>(base);
+    std::vector<int64_t> in_off, chk_off;
+    std::vector<uint8_t> bits;
+    std::vector<uint32_t> masks(pb, pb + m);
+    for (int j = 0; j < k; j++) in_off.push_back(j * frag_stride);
+    for (int p = 0; p < m; p++) {
+        chk_off.push_back((k + p) * frag_stride);
+        bits.push_back(static_cast<uint8_t>(k + p));
+    }
+    return check_generic(dev, stream, b, stripe_stride, chk_off.data(), bits.data(), m, 0, blocksize, nstripes, d_status,
+                         [&](int64_t f0, int64_t len, int s0, int ns, uint8_t* calc, int64_t pitch) {
+                             ApplyArgs a{};
+                             a.in_base = b + s0 * stripe_stride;
+                             a.in_stride = stripe_stride;
+                             a.out_base = calc;
+                             a.out_stride = m * pitch;
+                             std::vector<int64_t> io(in_off), oo;
+                             for (auto& v : io) v += f0;
+                             for (int r = 0; r < m; r++) oo.push_back(r * pitch);
+                             return launch_xor<false>(masks.data(), m, k, a, io.data(), oo.data(), len, ns, st);
+                         });
+}
+
+long long ecamd_check_fused_launches(void) { return g_check_fused.load(std::memory_order_relaxed); }
+
+int ecamd_check_prebuild(int k, int m, const int* missing, const char* arch, const char* dir)
+{
+    if (!arch || !dir) return fail(ECAMD_EINVAL, "null arch / dir");
+    if (k <= 0 || m < 0 || k + m > 32) return fail(ECAMD_EINVAL, "check needs k + m <= 32 (k=%d m=%d)", k, m);
+    std::vector<int> miss;
+    if (missing)
+        for (int i = 0; missing[i] > -1; i++) miss.push_back(missing[i]);
+    const std::vector<int> G = rs_generator(k, m);
+    FragmentMap fm;
+    if (G.empty() || rs_check_map(G, k, m, miss, fm) != 0)
+        return fail(ECAMD_EINVAL, "too many missing fragments (%zu > m=%d)", miss.size(), m);
+    const int R = static_cast<int>(fm.outputs.size()), K = static_cast<int>(fm.inputs.size());
+    int built = 0;
+    for (int row0 = 0; row0 < R; row0 += 8) {
+        const int nrows = std::min(8, R - row0);
+        BsForm f;
+        if (!bs_form(nrows, K + nrows, false, false, f)) continue;
+        const int r = ecamd::bitslice_prebuild(syndrome_rows(fm.coeff, K, row0, nrows), nrows, K + nrows, f.depth, false, 0,
+                                               f.wave, nullptr, f.prefetch, f.occ, arch, dir, true);
+        if (r < 0) return fail(ECAMD_EHIP, "check prebuild failed (%d) for a %dx%d map", r, nrows, K + nrows);
+        built += r;
+    }
+    return built;
 }
 
 }  // extern "C"

@@ -55,9 +55,12 @@ int side_join(int dev, void* stream);
 // on one stream are ordered, so reuse is safe (slot 1 holds values that must outlive a CRC pass on
 // the same stream, whose partials use slot 0).
 // Slot 4: the small-launch fused CRC's counter and partials (ecamd_map_apply_strided_crc).  A slot is
-// zeroed when it is (re)allocated.
-constexpr int kStreamScratchSlots = 5;
+// zeroed when it is (re)allocated.  Slot 5: the fragments ecamd_rs_check / ecamd_xor_check compute to
+// compare the stored ones against (generic path; at most kCheckScratchBytes).
+constexpr int kStreamScratchSlots = 6;
 constexpr int kSmallCrcScratchSlot = 4;
+constexpr int kCheckScratchSlot = 5;
+constexpr size_t kCheckScratchBytes = size_t(64) << 20;
 int stream_scratch(int dev, void* stream, int slot, size_t words, uint32_t** out);
 // A framed call in progress on (dev, stream): its context is not released until the call has
 // returned and its work on the stream has completed.

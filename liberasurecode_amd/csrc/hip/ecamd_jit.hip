@@ -9,6 +9,8 @@
 // a hash of the request and of the generator itself, so later processes load them at once.  Knob "bitslice": 1 (default)
 // launches the LDS-table kernel until the code object is ready, 2 waits for it (tests, bench), 0
 // never uses the bitsliced form; ecamd_bitslice_wait() waits for every compile started so far.
+// The check form (ecamd_rs_check: a syndrome map whose kernel writes status bits, no fragments) is one
+// more entry kind with its own requests and cache keys.
 #include <hip/hip_runtime.h>
 #include <dirent.h>
 #include <dlfcn.h>
@@ -205,6 +207,7 @@ struct BsEntry {
     std::vector<int> shifts;  // copy-through inputs' byte shifts (BitsliceStyle::in_shift), empty: none
     int prefetch = 0;         // one-wave form: chunks of the next input loaded ahead (BitsliceStyle::prefetch)
     BsOcc occ;                // one-wave form: amdgpu_waves_per_eu and input barrier (bitslice.hpp)
+    bool check = false;       // check form (BitsliceStyle::check): plain maps only
     int cap_index = 0;    // into kCaps: shared temporaries allowed (fewer: fewer registers)
     std::string arch;     // target of the code object (the requesting device's gcnArchName)
     std::string co_path;  // cache file of the code object
@@ -303,6 +306,11 @@ const std::string& generator_fingerprint()
              bitslice_source(tiny, 0, crc_shifted) + bitslice_source(tiny5, 0, wave_pf) +
              bitslice_source(tiny, 2, wave_ring) + bitslice_source(tiny, 0, wave_occ) +
              bitslice_source(tiny, 0, crc_wave) + bitslice_source(tiny, 2, copy_ring) + kBsNetworkVersion;
+        BitsliceStyle chk = wave, chk_tile;  // the check form: one-wave and 16 KiB tiles, registers and rings
+        chk.check = chk_tile.check = true;
+        const BitsliceNet syn = bitslice_network({3, 1}, 1, 2, 0);
+        fp += bitslice_source(syn, 0, chk) + bitslice_source(syn, 2, chk) + bitslice_source(syn, 0, chk_tile) +
+              bitslice_source(syn, 2, chk_tile);
     });
     return fp;
 }
@@ -330,7 +338,7 @@ std::string request_of(const BsEntry& e)
                                 : 0;
     return bitslice_request(e.coeff, e.R, e.K, kCaps[e.cap_index], e.depth, e.copy, e.crc > 0,
                             e.crc > 0 ? (e.crc & 7) : 1, (e.crc & 8) != 0, (e.crc & 16) != 0, e.wave, &e.shifts,
-                            e.prefetch, e.wave || e.occ.threads || cw ? &e.occ : nullptr, cw);
+                            e.prefetch, e.wave || e.occ.threads || cw ? &e.occ : nullptr, cw, e.check);
 }
 std::string object_name(const BsEntry& e)
 {
@@ -444,7 +452,7 @@ void wait_compile(std::unique_lock<std::mutex>& lk, const std::shared_ptr<BsEntr
 // kernels get equal requests.  Returns the key.
 std::vector<int> normalize(const std::vector<int>& coeff, int R, int K, int& depth, bool& copy, int& crc,
                            bool& wave, const std::vector<int>* in_shift, int& prefetch, std::vector<int>& shifts,
-                           BsOcc& occ)
+                           BsOcc& occ, bool& check)
 {
     if (crc) {  // position sets 1 / 2 / 4, + 8 for the lane-shift fold, + 16 for nibble piece tables;
         // + 32 for one-wave tiles (with the lane fold, byte tables) in workgroups of (crc >> 6) waves
@@ -453,6 +461,7 @@ std::vector<int> normalize(const std::vector<int>& coeff, int R, int K, int& dep
         crc = (pos >= 4 ? 4 : pos >= 2 ? 2 : 1) | (cw ? 8 | 32 | (cw << 6) | (crc & (1024 | 6144)) : crc & 24);
     }
     copy = copy || crc;
+    check = check && !copy;
     wave = wave && !crc;
     // the LDS ring: plain maps, and copy-through maps in one-wave tiles (not the crc variant)
     depth = crc || (copy && !wave) ? 0 : bitslice_depth(depth, K);
@@ -483,6 +492,7 @@ std::vector<int> normalize(const std::vector<int>& coeff, int R, int K, int& dep
         key.push_back(-1);
         key.insert(key.end(), shifts.begin(), shifts.end());
     }
+    if (check) key.push_back(-2);  // (no coefficient or shift is negative)
     return key;
 }
 
@@ -521,7 +531,7 @@ long code_object_scratch(const std::string& code)
 // 0: this form never takes a bitsliced kernel, < 0: the helper is missing or failed.
 int bitslice_prebuild(const std::vector<int>& coeff, int R, int K, int depth, bool copy, int crc, bool wave,
                       const std::vector<int>* in_shift, int prefetch, const BsOcc& occ_in, const std::string& arch,
-                      const std::string& dir)
+                      const std::string& dir, bool check)
 {
     if (R <= 0 || R > kBsMaxR || K <= 0 || K > kBsMaxK) return 0;
     const std::string helper = helper_path();
@@ -529,8 +539,9 @@ int bitslice_prebuild(const std::vector<int>& coeff, int R, int K, int depth, bo
     BsEntry e;
     std::vector<int> shifts;
     BsOcc occ = occ_in;
-    normalize(coeff, R, K, depth, copy, crc, wave, in_shift, prefetch, shifts, occ);
+    normalize(coeff, R, K, depth, copy, crc, wave, in_shift, prefetch, shifts, occ, check);
     e.occ = occ;
+    e.check = check;
     e.coeff = coeff;
     e.R = R;
     e.K = K;
@@ -578,14 +589,15 @@ int bitslice_prebuild(const std::vector<int>& coeff, int R, int K, int depth, bo
 // 1 the kernel is loaded, 0 compiling or queued, -1 unavailable (no code object can be had).
 hipFunction_t bitslice_function(int dev, const std::vector<int>& coeff, int R, int K, int depth, bool wait,
                                 std::shared_ptr<void>& hold, bool copy, int crc, bool wave,
-                                const std::vector<int>* in_shift, int prefetch, int* status, const BsOcc* occ_in)
+                                const std::vector<int>* in_shift, int prefetch, int* status, const BsOcc* occ_in,
+                                bool check)
 {
     if (status) *status = -1;
     if (R <= 0 || R > kBsMaxR || K <= 0 || K > kBsMaxK || (helper_path().empty() && shipped_dir().empty()))
         return nullptr;
     std::vector<int> shifts;
     BsOcc occ = occ_in ? *occ_in : BsOcc{};
-    const std::vector<int> key = normalize(coeff, R, K, depth, copy, crc, wave, in_shift, prefetch, shifts, occ);
+    const std::vector<int> key = normalize(coeff, R, K, depth, copy, crc, wave, in_shift, prefetch, shifts, occ, check);
     std::vector<std::shared_ptr<BsEntry>> evicted;  // released after the lock (declared before it)
     std::unique_lock<std::mutex> lk(g_jit_mu);
     for (size_t i = 0; i < g_running.size();) {  // reap finished compilers, freeing their slots
@@ -616,6 +628,7 @@ hipFunction_t bitslice_function(int dev, const std::vector<int>& coeff, int R, i
         slot->shifts = shifts;
         slot->prefetch = prefetch;
         slot->occ = occ;
+        slot->check = check;
         slot->arch = device_arch(dev);
         slot->cap_index = first_cap(R, crc, wave);
         start_compile(slot, wait);

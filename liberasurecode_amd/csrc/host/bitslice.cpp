@@ -358,7 +358,16 @@ std::string bitslice_source(const BitsliceNet& net, int depth, BitsliceStyle sty
     s << "// generated by liberasurecode_amd bitslice_source: " << net.R << " outputs x " << net.K
       << " inputs, " << net.xor_ops() << " network ops per tile, "
       << (D ? "LDS ring of " + std::to_string(D) + " inputs per wave" : std::string("register loads")) << "\n";
-    s << kPrelude;
+    const bool check = style.check && !style.crc && !style.copy_through;  // plain maps only
+    if (check) {
+        // the check form's kernarg struct ends with the status words (BsArgs); every other form keeps
+        // the prelude it always had
+        std::string pre(kPrelude);
+        const std::string tail = "    i32 crc_nfrag;\n};";
+        pre.replace(pre.find(tail), tail.size(), "    i32 crc_nfrag;\n    u32* status;\n    u8 status_bit[8];\n};");
+        s << pre;
+    } else
+        s << kPrelude;
     if (style.crc) s << kPreludeCrc;
     const int CW = style.crc ? std::clamp(style.crc_wave, 0, 16) : 0;  // one-wave crc form: waves per workgroup
     const int wpe = ((!style.crc || CW) && style.waves >= 1 && style.waves <= 8) ? style.waves
@@ -410,7 +419,10 @@ std::string bitslice_source(const BitsliceNet& net, int depth, BitsliceStyle sty
     // The one-wave LDS-ring form accumulates single terms through an asm XOR too: with plain `^=` the
     // compiler re-associates the sum of a 1-output map over the inputs (a tree over all 20 inputs'
     // planes at K = 20: 256 VGPRs + scratch), which the ring's inline-asm reads leave it free to do.
-    const bool opaque_xor = D != 0 && T == 64;
+    // The check form does so in every form: its last R inputs (the identity block of [A | I]) are single
+    // terms only, and with plain `^=` the compiler moves their loads and transposes about freely -- the
+    // 8 x 28 syndrome map of (20,8) then spills ~1 KiB per lane at every cap, and fits 250 VGPRs this way.
+    const bool opaque_xor = (D != 0 && T == 64) || check;
     // the network of input j on P[16] (bit planes), accumulated into acc
     auto network = [&](int j) {
         const auto& in = net.inputs[static_cast<size_t>(j)];
@@ -463,6 +475,20 @@ std::string bitslice_source(const BitsliceNet& net, int depth, BitsliceStyle sty
           << "; r++)\n#pragma unroll\n            for (int p = 0; p < 16; p++) acc[r][p] = 0u;\n";
     };
     auto outputs = [&](const char* rout, const char* off) {
+        if (check) {
+            // acc holds the syndrome planes of [A | I]: all zero on a consistent tile.  The ballot is
+            // wave-uniform, so a clean wave skips the atomic altogether; a dirty one sends a single lane.
+            s << "#pragma unroll\n        for (int r = 0; r < " << net.R
+              << "; r++) {\n"
+                 "            u32 o = acc[r][0];\n"
+                 "#pragma unroll\n"
+                 "            for (int p = 1; p < 16; p++) o |= acc[r][p];\n"
+                 "            if (__builtin_amdgcn_ballot_w64(o != 0u) != 0ull && (threadIdx.x & 63u) == 0u)\n"
+                 "                __hip_atomic_fetch_or(a.status + s, 1u << a.status_bit[r], __ATOMIC_RELAXED, "
+                 "__HIP_MEMORY_SCOPE_AGENT);\n"
+                 "        }\n";
+            return;
+        }
         s << "#pragma unroll\n        for (int r = 0; r < " << net.R
           << "; r++) {\n"
              "            tr16(acc[r]);\n"
@@ -1097,7 +1123,8 @@ std::string bitslice_source(const BitsliceNet& net, int depth, BitsliceStyle sty
 
 std::string bitslice_request(const std::vector<int>& coeff, int R, int K, int cap, int depth, bool copy,
                              bool crc, int crc_pos, bool crc_lane, bool crc_nib, bool wave,
-                             const std::vector<int>* in_shift, int prefetch, const BsOcc* occ, int crc_wave)
+                             const std::vector<int>* in_shift, int prefetch, const BsOcc* occ, int crc_wave,
+                             bool check)
 {
     std::ostringstream s;
     // flags: bit 0 copy-through, bit 1 crc (which copies too), bits 2-3 log2 of the crc position
@@ -1144,13 +1171,16 @@ std::string bitslice_request(const std::vector<int>& coeff, int R, int K, int ca
     } else
         s << "ecamd-bitslice-request 1\n" << R << " " << K << " " << cap << " " << depth << "\n";
     for (size_t i = 0; i < coeff.size(); i++) s << coeff[i] << ((i + 1) % static_cast<size_t>(K) ? " " : "\n");
+    // the check form (plain maps only): a trailing word, written only when set, so every other
+    // request reads as it always did
+    if (check && !copy && !crc) s << "check\n";
     return s.str();
 }
 
 bool bitslice_parse_request(const std::string& text, std::vector<int>& coeff, int& R, int& K, int& cap,
                             int& depth, bool* copy, bool* crc, int* crc_pos, bool* crc_lane, bool* crc_nib,
                             bool* wave, bool* budget2, std::vector<int>* in_shift, int* prefetch, BsOcc* occ,
-                            int* crc_wave)
+                            int* crc_wave, bool* check)
 {
     std::istringstream s(text);
     std::string magic;
@@ -1211,6 +1241,10 @@ bool bitslice_parse_request(const std::string& text, std::vector<int>& coeff, in
     coeff.assign(static_cast<size_t>(R) * K, 0);
     for (int& c : coeff)
         if (!(s >> c) || c < 0 || c > 0xffff) return false;
+    std::string word;
+    const bool chk = static_cast<bool>(s >> word);
+    if (chk && (word != "check" || (cp & 3))) return false;  // plain maps only
+    if (check) *check = chk;
     return true;
 }
 

@@ -113,6 +113,11 @@ struct BitsliceStyle {
     // (through the vector L1) instead of LDS -- a second lookup engine for the random-index lookups
     // whose LDS bank conflicts bound the form (round 6 A/B, knob frame_crc_wave_l1)
     bool crc_l1 = false;
+    // plain forms only (ecamd_rs_check): the map is the syndrome matrix [A | I_R] -- the last R inputs
+    // are the stored fragments under test -- and the epilogue writes no fragment: per row it ORs the 16
+    // accumulator planes, and a wave that sees a non-zero OR has one lane OR bit status_bit[r] into
+    // status[stripe] (BsArgs; a global atomic at agent scope).  A consistent stripe causes no write.
+    bool check = false;
 };
 // LDS words of the CRC image the crc variant reads (host/crc.hpp build_fused_crc_image_pos: byte
 // piece tables per position, chain step 4096 B): npos x 4 x 1024 piece words + gap + 6 butterfly
@@ -147,12 +152,13 @@ struct BsOcc {
 std::string bitslice_request(const std::vector<int>& coeff, int R, int K, int cap, int depth, bool copy = false,
                              bool crc = false, int crc_pos = 1, bool crc_lane = false, bool crc_nib = false,
                              bool wave = false, const std::vector<int>* in_shift = nullptr, int prefetch = 0,
-                             const BsOcc* occ = nullptr, int crc_wave = 0);
+                             const BsOcc* occ = nullptr, int crc_wave = 0, bool check = false);
 bool bitslice_parse_request(const std::string& text, std::vector<int>& coeff, int& R, int& K, int& cap,
                             int& depth, bool* copy = nullptr, bool* crc = nullptr, int* crc_pos = nullptr,
                             bool* crc_lane = nullptr, bool* crc_nib = nullptr, bool* wave = nullptr,
                             bool* budget2 = nullptr, std::vector<int>* in_shift = nullptr,
-                            int* prefetch = nullptr, BsOcc* occ = nullptr, int* crc_wave = nullptr);
+                            int* prefetch = nullptr, BsOcc* occ = nullptr, int* crc_wave = nullptr,
+                            bool* check = nullptr);
 
 // Kernel arguments (layout shared by the generated source and the launcher).
 constexpr int kBsTile = 16384;  // bytes of each fragment per workgroup tile (256 lanes x 64 B)
@@ -186,6 +192,10 @@ struct BsArgs {
     int32_t crc_q;
     int32_t crc_per;
     int32_t crc_nfrag;
+    // check form (BitsliceStyle::check; only its generated prelude declares these two): row r of
+    // stripe s ORs 1 << status_bit[r] into status[s] when its syndrome is not zero
+    uint32_t* status;
+    uint8_t status_bit[kBsMaxR];
 };
 
 }  // namespace ecamd

@@ -247,4 +247,26 @@ int rs_reconstruct_map(const std::vector<int>& G, int k, int m, const std::vecto
     return 0;
 }
 
+int rs_check_map(const std::vector<int>& G, int k, int m, const std::vector<int>& missing,
+                 FragmentMap& out)
+{
+    Availability av;
+    if (!availability(k, m, missing, av)) return -1;
+    std::vector<int> inv;
+    if (!decode_inverse(G, k, av.first_k, inv)) return -1;
+    const GF16& gf = GF16::get();
+    out = FragmentMap();
+    out.inputs = av.first_k;
+    for (int f = 0; f < k + m; f++) {
+        if (av.missing[f] || std::find(av.first_k.begin(), av.first_k.end(), f) != av.first_k.end()) continue;
+        out.outputs.push_back(f);
+        for (int c = 0; c < k; c++) {
+            int v = 0;
+            for (int d = 0; d < k; d++) v ^= gf.mul(G[f * k + d], inv[d * k + c]);
+            out.coeff.push_back(v);
+        }
+    }
+    return 0;
+}
+
 }  // namespace ecamd

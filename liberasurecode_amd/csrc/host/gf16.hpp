@@ -60,6 +60,13 @@ int rs_decode_map(const std::vector<int>& G, int k, int m, const std::vector<int
 int rs_reconstruct_map(const std::vector<int>& G, int k, int m, const std::vector<int>& missing,
                        int dest, FragmentMap& out);
 
+// Check map (ecamd_rs_check): the first k available fragments as inputs, every OTHER available
+// fragment as an output, ascending; row f = G[f] * inv(G[inputs]) is the value the inputs imply for
+// fragment f (nothing missing: the generator's parity rows, the encode map).  Returns 0, or -1 when
+// more than m fragments are missing; with exactly m missing there are no outputs.
+int rs_check_map(const std::vector<int>& G, int k, int m, const std::vector<int>& missing,
+                 FragmentMap& out);
+
 // Encode map: inputs 0..k-1, outputs k..k+m-1, generator parity rows.
 FragmentMap rs_encode_map(const std::vector<int>& G, int k, int m);
 

@@ -153,6 +153,37 @@ def rs_reconstruct(k, m, missing, dest, lay: Layout, stream=None):
                                      lay.nstripes, _s(stream)), "rs_reconstruct")
 
 
+def _status(call, lay, stream, what):
+    """Run call(d_status) and return the nstripes status words (waits for `stream`)."""
+    buf = DeviceBuffer(4 * max(lay.nstripes, 1))
+    try:
+        check(call(buf.ptr), what)
+        if stream is not None:
+            stream.synchronize()
+        return buf.download(4 * lay.nstripes).view(np.uint32).copy()
+    finally:
+        buf.free()
+
+
+def rs_check(k, m, lay: Layout, missing=(), stream=None):
+    """ecamd_rs_check: (status, checked_mask).  status[s] has bit f set when available fragment f of
+    stripe s -- one that is not among the first k available, the inputs -- differs from what the
+    inputs imply; checked_mask has the bits of the fragments that were checked."""
+    checked = C.c_uint32(0)
+    status = _status(lambda d: dev().ecamd_rs_check(
+        k, m, ints(list(missing) + [-1]), lay.buf.ptr, lay.stripe_stride, lay.frag_stride, lay.blocksize,
+        lay.nstripes, d, C.byref(checked), _s(stream)), lay, stream, "rs_check")
+    return status, checked.value
+
+
+def xor_check(k, m, hd, lay: Layout, stream=None):
+    """ecamd_xor_check: status[s] has bit k + p set when stored parity p of stripe s differs from the
+    XOR its parity bitmap names."""
+    return _status(lambda d: dev().ecamd_xor_check(
+        k, m, hd, lay.buf.ptr, lay.stripe_stride, lay.frag_stride, lay.blocksize, lay.nstripes, d,
+        _s(stream)), lay, stream, "xor_check")
+
+
 class GF16Map:
     """An arbitrary R x K GF(2^16) fragment map prepared on the device."""
 
