@@ -135,6 +135,15 @@ long long ecamd_small_server_posts(void);
 long long ecamd_small_server_launches(void);
 /* Posts that wrote a new argument block into one of the server's two slots (the others reused a cached one). */
 long long ecamd_small_server_rewrites(void);
+/* Posts that matched a cached slot in everything except the map's serial: another map of the same shape whose
+ * table image sits at a recycled device address.  They rewrite the slot like any other new request (a map is
+ * identified by the serial it got at creation, never by its tables' address). */
+long long ecamd_small_server_stale_hits(void);
+/* Stops the calling thread's server and waits for its kernel to exit (after a failed
+ * ecamd_small_server_wait): nothing it was handed is in use afterwards, its cached argument blocks are
+ * forgotten and its counters zeroed; the next post launches it again.  0 (also without a server), or < 0 when
+ * its stream cannot be synchronized -- then memory a pending request points to must not be reused. */
+int ecamd_small_server_quiesce(void);
 
 /* Pointer tables in device memory: input j of stripe s is d_in_ptrs[s*in_row + in_col[j]],
  * output r is d_out_ptrs[s*out_row + out_col[r]] (in_col / out_col are host arrays). */
@@ -280,7 +289,9 @@ int ecamd_percall_tee_arm(int n, const void *const *key, const void *const *src,
                           const int64_t *len);
 void ecamd_percall_tee_disarm(int64_t *done);
 /* Fault injection for tests: site "staging" makes the next `count` staging acquisitions of the
- * synchronous host-buffer calls fail with ECAMD_ENOMEM (0 disarms). */
+ * synchronous host-buffer calls fail with ECAMD_ENOMEM (0 disarms); site "server_wait" makes the next
+ * `count` waits for a request posted to the resident small server report ECAMD_EHIP right after the post,
+ * without waiting, as a timed-out ecamd_small_server_wait would (the request itself is not disturbed). */
 int ecamd_fault_inject(const char *site, int count);
 
 /* ---- on-device framing: the wire format of liberasurecode_encode, in HBM ----

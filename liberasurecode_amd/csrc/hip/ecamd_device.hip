@@ -28,6 +28,7 @@
 #include "ecamd_host.h"
 #include "ecamd_internal.hpp"
 #include "ecamd_kernels.hpp"
+#include "ecamd_server_slots.hpp"
 #include "ecamd_frame.hpp"
 
 using namespace ecamd;
@@ -508,6 +509,9 @@ struct ecamd_map {
     std::vector<Pass> passes;
     uint8_t* d_tables = nullptr;
     std::vector<int> coeff;  // R x K (host copy: the bitsliced kernels are generated from it)
+    // this map's identity for whatever caches its tables (the resident small server's slots): from a
+    // process-wide counter at creation, never reused -- d_tables' address is, once the map is destroyed
+    uint64_t serial = 0;
 };
 
 namespace ecamd {
@@ -721,9 +725,7 @@ struct SmallServer {
     uint32_t key = 0;  // of the launched kernel: W | G << 4, or kSmallServerXor
     uint32_t post = 0, prev = 0, seq = 0;
     bool running = false;
-    bool have_args[2] = {false, false};  // box slot i holds last_args[i] (this server instance)
-    SmallArgs last_args[2]{};
-    uint32_t last_variant[2] = {0, 0};
+    ServerSlotEntry<SmallArgs> cached[2];  // box slot i holds cached[i].args (this server instance)
     uint32_t gen[2] = {0, 0};  // slot generations (8 bits in the post word)
     int last_slot = 0;
     std::chrono::steady_clock::time_point last{};
@@ -734,7 +736,7 @@ constexpr size_t kServerLds = kLdsBytes - 1024;  // the server's dynamic LDS (it
 static_assert(2 * static_cast<size_t>(kSmallServerLdsHalf) <= kServerLds, "two table placements");
 std::mutex g_srv_mu;
 auto& g_srv_free = *new std::vector<SmallServer*>();  // idle servers of exited threads (never freed)
-std::atomic<long long> g_srv_posts{0}, g_srv_launches{0}, g_srv_rewrites{0};
+std::atomic<long long> g_srv_posts{0}, g_srv_launches{0}, g_srv_rewrites{0}, g_srv_stale_hits{0};
 int g_srv_count = 0;
 
 // ECAMD_PERCALL_SERVER_IDLE_US: how long a server polls without a request (default 2000 us)
@@ -824,8 +826,8 @@ int server_launch(SmallServer* sv, uint32_t key, uint32_t post0, bool dup)
 }
 
 // Posts the small launch `s` (variant, nblk workgroups, lds bytes) to the calling thread's server: 0 posted,
-// 1 not taken (the caller launches it), < 0 an error.
-int server_post(SmallArgs& s, uint32_t variant, unsigned nblk, size_t lds, bool crc)
+// 1 not taken (the caller launches it), < 0 an error.  `serial`: of the map s.tables belongs to (0: no tables).
+int server_post(SmallArgs& s, uint32_t variant, uint64_t serial, unsigned nblk, size_t lds, bool crc)
 {
     if (nblk == 0 || nblk > static_cast<unsigned>(kSmallServerWgs) || lds > kServerLds) return 1;
     int dev = 0;
@@ -856,29 +858,20 @@ int server_post(SmallArgs& s, uint32_t variant, unsigned nblk, size_t lds, bool 
         const int rc = server_launch(sv, key, sv->post, false);
         if (rc) return rc;
     }
-    // a cached request's arguments but for the flag value (the common case: one caller repeating one
-    // operation, or alternating two, on one size): the slot is not rewritten and the server keeps its copy
-    // (and its staged tables when they are that slot's)
-    if (launch) sv->have_args[0] = sv->have_args[1] = false;  // (a new instance holds no block: new generations)
-    int slot = -1;
-    for (int i = 0; i < 2 && slot < 0; i++) {
-        if (!sv->have_args[i] || sv->last_variant[i] != variant) continue;
-        SmallArgs cmp = s;
-        cmp.done_val = sv->last_args[i].done_val;
-        if (std::memcmp(&cmp, &sv->last_args[i], sizeof(SmallArgs)) == 0) slot = i;
-    }
-    const bool same = slot >= 0;
-    if (!same) {  // the slot not used last
-        slot = sv->last_slot ^ 1;
+    // a cached request's arguments but for the flag value, of the same map (the common case: one caller
+    // repeating one operation, or alternating two, on one size): the slot is not rewritten and the server
+    // keeps its copy (and its staged tables when they are that slot's) -- server_slot_choose
+    if (launch) sv->cached[0].have = sv->cached[1].have = false;  // (a new instance holds no block: new generations)
+    const ServerSlotChoice ch = server_slot_choose(s, variant, serial, sv->cached, sv->last_slot);
+    const int slot = ch.slot;
+    if (ch.stale) g_srv_stale_hits.fetch_add(1, std::memory_order_relaxed);
+    if (ch.rewrite) {  // the slot not used last
         std::memcpy(&sv->box->slot[slot].args, &s, sizeof(SmallArgs));
         sv->box->variant[slot] = variant;
-        sv->last_args[slot] = s;
-        sv->last_variant[slot] = variant;
-        sv->have_args[slot] = true;
         sv->gen[slot] = (sv->gen[slot] + 1u) & 0xffu;
         g_srv_rewrites.fetch_add(1, std::memory_order_relaxed);
     }
-    sv->last_slot = slot;
+    server_slot_note(ch, s, variant, serial, sv->cached, sv->last_slot);
     sv->seq = sv->seq % 0x3fffu + 1u;
     sv->prev = sv->post;
     sv->post = (sv->seq << 18) | (sv->gen[slot] << 10) | (slot ? kSmallServerSlot : 0u) |
@@ -901,7 +894,8 @@ bool server_wanted(bool crc, bool only, bool st_in, int nstripes, const SmallArg
 // ends the operation (the completion flag may be attached to it); `only`: it is the whole operation (then
 // it may be posted to the resident small server).
 int launch_small(const ApplyArgs& a, const ecamd_map::Pass& p, int64_t bs, int nstripes, const uint8_t* tables,
-                 hipStream_t st, const SmallCrcReq* crc = nullptr, bool last = false, bool only = false)
+                 uint64_t serial, hipStream_t st, const SmallCrcReq* crc = nullptr, bool last = false,
+                 bool only = false)
 {
     const int lane = g_tune.small_lane ? static_cast<int>(g_tune.small_lane)
                                        : ((bs + 1) / 2 * nstripes <= 256 ? 2 : 4);
@@ -931,7 +925,7 @@ int launch_small(const ApplyArgs& a, const ecamd_map::Pass& p, int64_t bs, int n
         std::copy(k.minv, k.minv + 32, s.crc_minv);
         s.crc_c = k.c;
         if (server_wanted(true, only, st_in, nstripes, s)) {
-            const int r = server_post(s, static_cast<uint32_t>(width | (lane << 4) | 256), grid.x, lds, true);
+            const int r = server_post(s, static_cast<uint32_t>(width | (lane << 4) | 256), serial, grid.x, lds, true);
             if (r < 0) return r;
             if (r == 0) {
                 t_done.taken = t_done.served = true;
@@ -956,7 +950,7 @@ int launch_small(const ApplyArgs& a, const ecamd_map::Pass& p, int64_t bs, int n
         return 0;
     }
     if ((lane == 2 || lane == 4) && server_wanted(false, only, st_in, nstripes, s)) {
-        const int r = server_post(s, static_cast<uint32_t>(width | (lane << 4)), grid.x, lds, false);
+        const int r = server_post(s, static_cast<uint32_t>(width | (lane << 4)), serial, grid.x, lds, false);
         if (r < 0) return r;
         if (r == 0) {
             t_done.taken = t_done.served = true;
@@ -1010,7 +1004,7 @@ int launch_xor_small(const ApplyArgs& a, int64_t bs, int nstripes, hipStream_t s
     const size_t stage = static_cast<size_t>(crc ? a.ncols + a.nrows : a.ncols) * 1024 +
                          (crc ? static_cast<size_t>(small_crc_words(4)) * 4 : 0);
     if (server_wanted(crc != nullptr, only, st_in, nstripes, s)) {
-        const int r = server_post(s, kSmallServerXor | (crc ? 256u : 0u), grid, stage, crc != nullptr);
+        const int r = server_post(s, kSmallServerXor | (crc ? 256u : 0u), 0, grid, stage, crc != nullptr);
         if (r < 0) return r;
         if (r == 0) {
             t_done.taken = t_done.served = true;
@@ -1526,8 +1520,8 @@ int launch_gf16(const ecamd_map* map, ApplyArgs base_args, const int64_t* in_off
             }
         }
         if (!PTRS && small_launch(a, bs, nstripes)) {
-            int rc = launch_small(a, p, bs, nstripes, map->d_tables, st, nullptr, &p == &map->passes.back(),
-                                  map->passes.size() == 1 && done == 0);
+            int rc = launch_small(a, p, bs, nstripes, map->d_tables, map->serial, st, nullptr,
+                                  &p == &map->passes.back(), map->passes.size() == 1 && done == 0);
             if (rc) return rc;
             continue;
         }
@@ -2963,7 +2957,9 @@ int ecamd_map_create(const int* coeff, int R, int K, ecamd_map** out)
         auto n = build_nibble_tables(c, R, K, p.row0, p.width, p.col0, p.ncols);
         std::memcpy(img.data() + p.nib_offset, n.data(), n.size());
     }
+    static std::atomic<uint64_t> next_serial{0};
     auto* map = new ecamd_map();
+    map->serial = next_serial.fetch_add(1, std::memory_order_relaxed) + 1;
     map->device = dev;
     map->R = R;
     map->K = K;
@@ -3075,7 +3071,8 @@ int ecamd_map_apply_strided_crc(const ecamd_map* map, const void* in_base, const
     if ((rc = stream_scratch(dev, stream, kSmallCrcScratchSlot, 16 + static_cast<size_t>(map->K + map->R) * wgs,
                              &req.part)))
         return rc;
-    rc = launch_small(a, p, blocksize, 1, map->d_tables, static_cast<hipStream_t>(stream), &req, true, true);
+    rc = launch_small(a, p, blocksize, 1, map->d_tables, map->serial, static_cast<hipStream_t>(stream), &req, true,
+                      true);
     if (rc == 0) g_small_crc_launches.fetch_add(1, std::memory_order_relaxed);
     return rc == ECAMD_EINVAL ? 1 : rc;
 }
@@ -3139,6 +3136,25 @@ int ecamd_done_flag_taken(void)
 long long ecamd_small_server_posts(void) { return g_srv_posts.load(std::memory_order_relaxed); }
 long long ecamd_small_server_launches(void) { return g_srv_launches.load(std::memory_order_relaxed); }
 long long ecamd_small_server_rewrites(void) { return g_srv_rewrites.load(std::memory_order_relaxed); }
+long long ecamd_small_server_stale_hits(void) { return g_srv_stale_hits.load(std::memory_order_relaxed); }
+
+int ecamd_small_server_quiesce(void)
+{
+    SmallServer* sv = t_srv.s;
+    if (!sv) return 0;
+    // as server_post stops it for another kernel key: every workgroup exits at its next poll
+    __atomic_store_n(&sv->box->stop, 1u, __ATOMIC_RELEASE);
+    const hipError_t e = hipStreamSynchronize(sv->st);
+    if (e != hipSuccess) return fail(ECAMD_EHIP, "small server: stop: %s", hipGetErrorString(e));
+    __atomic_store_n(&sv->box->stop, 0u, __ATOMIC_RELEASE);
+    sv->running = false;
+    sv->cached[0].have = sv->cached[1].have = false;
+    // workgroups that saw stop before the request sat it out while others ran and counted: the self-resetting
+    // done and checksum counters may be left above 0 (as in ecamd_small_server_wait's relaunch)
+    HIP_TRY(hipMemsetAsync(sv->scratch, 0, (64 + 16) * 4, sv->st));
+    HIP_TRY(hipStreamSynchronize(sv->st));
+    return 0;
+}
 
 int ecamd_small_server_wait(const uint32_t* flag, uint32_t value)
 {

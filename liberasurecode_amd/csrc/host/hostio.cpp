@@ -73,6 +73,16 @@ int note_exec(int rc)
 // Fault injection (ecamd_fault_inject): the next N staging acquisitions fail as an allocation
 // failure would, before any GPU work.
 std::atomic<int> g_fail_staging{0};
+// site "server_wait": the next N waits for a request posted to the resident small server fail right after
+// the post, as a timed-out ecamd_small_server_wait would.
+std::atomic<int> g_fail_server_wait{0};
+
+bool take_fault(std::atomic<int>& left_of)
+{
+    for (int left = left_of.load(); left > 0; left = left_of.load())
+        if (left_of.compare_exchange_weak(left, left - 1)) return true;
+    return false;
+}
 
 // zlib crc32_combine: crc(A || B) = A^|B| crc(A) ^ crc(B) for both checksum machines.
 uint32_t crc_combine(bool legacy, uint32_t a, uint32_t b, int64_t len_b)
@@ -212,6 +222,18 @@ struct MapHolder {
 std::mutex g_map_mu;
 std::map<std::vector<int>, std::shared_ptr<MapHolder>> g_maps;
 
+// ECAMD_PERCALL_MAP_CACHE: cached_map drops every cached matrix once it holds more than this many
+// (default 4096, at least 1)
+size_t map_cache_limit()
+{
+    static const size_t v = [] {
+        const char* env = std::getenv("ECAMD_PERCALL_MAP_CACHE");
+        const long long x = env && *env ? std::atoll(env) : 4096;
+        return static_cast<size_t>(std::clamp<long long>(x, 1, 1 << 24));
+    }();
+    return v;
+}
+
 std::shared_ptr<MapHolder> cached_map(int dev, const int* coeff, int R, int K, int* rc)
 {
     std::vector<int> key = {dev, R, K};
@@ -225,7 +247,9 @@ std::shared_ptr<MapHolder> cached_map(int dev, const int* coeff, int R, int K, i
     *rc = ecamd_map_create(coeff, R, K, &h->map);
     if (*rc) return nullptr;
     std::lock_guard<std::mutex> lk(g_map_mu);
-    if (g_maps.size() > 4096) g_maps.clear();  // holders in flight keep their map alive
+    // holders in flight keep their map alive; a dropped map's table address may come back for the next map of
+    // its shape, which is why the small server's slots go by ecamd_map's serial, not the address
+    if (g_maps.size() > map_cache_limit()) g_maps.clear();
     return g_maps.emplace(key, h).first->second;
 }
 
@@ -337,11 +361,10 @@ int grow(Staging* st, int64_t bytes)
 
 Staging* acquire(int dev, int64_t bytes, int* rc)
 {
-    for (int left = g_fail_staging.load(); left > 0; left = g_fail_staging.load())
-        if (g_fail_staging.compare_exchange_weak(left, left - 1)) {
-            *rc = ECAMD_ENOMEM;
-            return nullptr;
-        }
+    if (take_fault(g_fail_staging)) {
+        *rc = ECAMD_ENOMEM;
+        return nullptr;
+    }
     Staging* st = nullptr;
     {
         std::lock_guard<std::mutex> lk(g_pool_mu);
@@ -452,6 +475,7 @@ int run_chunked(int dev, int K, int R, const char* const* in, char* const* out, 
     // caller polls it instead of synchronizing the stream (falls back to that after kDonePollUs)
     bool flagged[2] = {false, false};
     bool served[2] = {false, false};  // posted to the resident small server: its stream, not the slot's
+    bool quarantine = false;  // a served wait failed and the server could not be stopped: the slabs are never reused
     uint32_t flag_val[2] = {0, 0};
     std::vector<void*> cdst(static_cast<size_t>(nfr));
     std::vector<const void*> csrc(static_cast<size_t>(nfr));
@@ -464,7 +488,13 @@ int run_chunked(int dev, int K, int R, const char* const* in, char* const* out, 
         int r = 0;
         if (served[s]) {
             const uint32_t* fw = done_word(st->slot[s].h_pin, st->cap);
-            if (!poll_done(fw, flag_val[s])) r = ecamd_small_server_wait(fw, flag_val[s]);
+            if (take_fault(g_fail_server_wait))
+                r = ECAMD_EHIP;
+            else if (!poll_done(fw, flag_val[s]))
+                r = ecamd_small_server_wait(fw, flag_val[s]);
+            // the request may still be live, and the server keeps argument blocks that point into this slab:
+            // stop the server and forget them before the slab goes back to the pool -- or keep the slab out
+            if (r && ecamd_small_server_quiesce() != 0) quarantine = true;
         } else if (!(flagged[s] && poll_done(done_word(st->slot[s].h_pin, st->cap), flag_val[s]))) {
             r = wait_stream(st->slot[s].stream, chunk * nfr >= kSpinMinBytes);
         }
@@ -583,7 +613,7 @@ int run_chunked(int dev, int K, int R, const char* const* in, char* const* out, 
         int r = drain(s);
         if (rc == 0) rc = r;
     }
-    release(st);
+    if (!quarantine) release(st);  // else leaked on purpose: the GPU may still write it
     // the outputs' bytes changed: drop what was recorded for them (an earlier call's input, or an output
     // that is also an input: flat XOR applies in place)
     auto overlaps_out = [&](const void* p, int64_t len) {
@@ -769,8 +799,13 @@ int ecamd_percall_status(void) { return t_exec_rc; }
 
 int ecamd_fault_inject(const char* site, int count)
 {
-    if (!site || std::strcmp(site, "staging") != 0 || count < 0) return ECAMD_EINVAL;
-    g_fail_staging.store(count);
+    if (!site || count < 0) return ECAMD_EINVAL;
+    if (std::strcmp(site, "staging") == 0)
+        g_fail_staging.store(count);
+    else if (std::strcmp(site, "server_wait") == 0)
+        g_fail_server_wait.store(count);
+    else
+        return ECAMD_EINVAL;
     return 0;
 }
 
