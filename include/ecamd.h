@@ -209,7 +209,7 @@ int ecamd_rs_reconstruct(int k, int m, const int *missing, int dest, void *base,
  * never influence the status.  Framed fragments (ecamd_frame_encode) are checked by passing
  * d_frags + 80 as `base`: the payload follows the 80-byte header, and 80 is a multiple of 16.
  * Reading the status: a single parity bit -- that parity fragment is bad; all checked bits -- an input
- * (or several fragments) is bad; re-check with a suspect listed as missing to isolate it.
+ * (or several fragments) is bad; re-check with a suspect listed as missing to isolate it, or let ecamd_rs_locate (below) name it in one pass.
  * Whole bitsliced tiles run one read-only fused kernel (the codec's XOR network over the K inputs and
  * the checked fragments; a consistent stripe causes no write); tails, small fragments, shapes the
  * bitsliced form declines, maps still compiling (knob "bitslice" 1) and knob "bitslice" 0 compute the
@@ -229,6 +229,57 @@ long long ecamd_check_fused_launches(void);
 /* Build time, as ecamd_bitslice_prebuild: the fused check kernel(s) of (k, m, missing).  Returns the
  * number of code objects present (0: the check takes no bitsliced form), < 0 on error. */
 int ecamd_check_prebuild(int k, int m, const int *missing, const char *arch, const char *dir);
+
+/* ---- locate and scrub: WHICH fragment of an inconsistent stripe is bad, and its repair ----
+ * ecamd_rs_locate runs the check above (same inputs / checked fragments, same d_status words, same
+ * *checked) and, in the same pass, fills d_suspects (nstripes uint32, device memory): 0 where
+ * d_status[s] is 0; otherwise the mask of participating fragments (inputs and checked) that ALONE
+ * explain every disagreement of stripe s.  Exactly one bit: that fragment is located -- list it as
+ * missing and decode.  Zero: more than one fragment is bad.  Bits of missing fragments and bits
+ * >= k+m are never set.  Only these two arrays are written; asynchronous on stream.
+ * How much can be told depends on R, the number of checked fragments (m minus the missing ones):
+ *   R >= 3  one bad fragment is located; any two bad fragments leave no suspect.
+ *   R == 2  one bad fragment is located; two bad fragments can in principle be attributed to a
+ *           third (a single suspect that is wrong) -- the code corrects one error with two checks
+ *           and cannot also detect a second.
+ *   R == 1  nothing can be told apart: every participating fragment is a suspect on a dirty stripe.
+ *   R == 0  both words are 0.
+ * The rule, per 16-bit word with syndromes S_r = stored_r ^ (what the inputs imply): input j explains
+ * the word iff S_r == (A[r][j] / A[0][j]) * S_0 for every r >= 1, checked fragment c iff S_r == 0 for
+ * every r != c; a stripe's suspects are the AND over its dirty words.
+ * ECAMD_EINVAL as for the check, and also for an ODD blocksize (the trailing byte's product is cut
+ * to 8 bits, so proportionality cannot be tested; the frontend and ecamd_frame_geometry only produce
+ * even sizes).  On every ECAMD_EINVAL both arrays are untouched.
+ * Whole bitsliced tiles with 2..8 checked fragments run the locate form of the fused check kernel (a
+ * clean tile costs what the check costs; a wave that sees a non-zero syndrome tests every candidate
+ * in registers and issues one atomic AND); everything else goes through the check's scratch path
+ * with a compare kernel that applies the same rule (DESIGN.md "Locate and scrub"). */
+int ecamd_rs_locate(int k, int m, const int *missing, const void *base, int64_t stripe_stride,
+                    int64_t frag_stride, int64_t blocksize, int nstripes, uint32_t *d_status,
+                    uint32_t *d_suspects, uint32_t *checked, void *stream);
+/* flat_xor_hd, all fragments present: the same rule over the 0/1 parity bitmaps -- data fragment j
+ * explains a word iff every parity that contains j has the same syndrome as the first one that does
+ * and every other parity has none; parity p iff only its own syndrome is non-zero.  A flat XOR code
+ * is not MDS: two bad fragments can leave a (wrong) single suspect. */
+int ecamd_xor_locate(int k, int m, int hd, const void *base, int64_t stripe_stride, int64_t frag_stride,
+                     int64_t blocksize, int nstripes, uint32_t *d_status, uint32_t *d_suspects,
+                     void *stream);
+/* Scrub FULL stripes (nothing missing; m >= 2, else ECAMD_EINVAL) in place: ecamd_rs_locate, a wait
+ * for `stream`, then ecamd_rs_decode_multi (rebuild_parity 1) with the list {f} for every stripe
+ * that has exactly one suspect f and the empty list for every other.  The counts (host, may be NULL)
+ * are final on return: consistent stripes, stripes being repaired, and dirty stripes with zero or
+ * several suspects, which are not written.  The repair launches are enqueued on stream; d_status and
+ * d_suspects keep what locate found.  With m == 2 a stripe with two bad fragments may be "repaired"
+ * towards a third (see R == 2 above). */
+int ecamd_rs_scrub(int k, int m, void *base, int64_t stripe_stride, int64_t frag_stride,
+                   int64_t blocksize, int nstripes, uint32_t *d_status, uint32_t *d_suspects,
+                   int *n_clean, int *n_repaired, int *n_unlocated, void *stream);
+/* Fused locate launches enqueued by this process (tests pin which path ran). */
+long long ecamd_locate_fused_launches(void);
+/* Build time, as ecamd_check_prebuild: the fused locate kernel of (k, m, missing).  Returns the number
+ * of code objects present (0: no fused form -- fewer than 2 or more than 8 checked fragments, a shape
+ * the bitsliced form declines, or a kernel that would need scratch), < 0 on error. */
+int ecamd_locate_prebuild(int k, int m, const int *missing, const char *arch, const char *dir);
 
 /* ---- flat_xor_hd on strided batches: the reference's xor_code_encode,
  * xor_hd_decode (decode_parity as its argument) and xor_reconstruct_one

@@ -15,6 +15,8 @@
  *                                     expressed directly over the first k available fragments
  *   ecamd_rs_check_map                the same algebra for every surviving fragment beyond the first
  *                                     k: what the inputs imply it holds (no reference counterpart)
+ *   ecamd_rs_locate_map               the check map with each column's ratios to its first row: which
+ *                                     single fragment explains a syndrome (no reference counterpart)
  *   ecamd_rs_reconstruct_map          coefficient row of liberasurecode_rs_vand_reconstruct
  *                                     (liberasurecode_rs_vand.c:483-558)
  */
@@ -54,6 +56,14 @@ int ecamd_rs_reconstruct_map(const int *G, int k, int m, const int *missing, int
  * missing leaves *ncheck 0. */
 int ecamd_rs_check_map(const int *G, int k, int m, const int *missing, int *inputs, int *checked,
                        int *coeff, int *ncheck);
+
+/* Locate map (ecamd_rs_locate, ecamd.h): what ecamd_rs_check_map returns, plus ratio[(*ncheck - 1) * k]
+ * with ratio[(r - 1) * k + j] = coeff[r * k + j] / coeff[j] (nothing for *ncheck < 2; ratio may then be
+ * NULL).  One bad input j leaves every word's syndrome S_r = coeff[r][j] * e, so it is the one j with
+ * S_r == ratio[r - 1][j] * S_0 for all r >= 1; one bad checked fragment leaves every other row zero.
+ * Every entry of a check map of this code is non-zero.  -1 if more than m missing. */
+int ecamd_rs_locate_map(const int *G, int k, int m, const int *missing, int *inputs, int *checked,
+                        int *coeff, int *ncheck, int *ratio);
 
 /* LDS split-table image for rows [row0,row0+width) x inputs [col0,col0+ncols) of the R x K
  * matrix coeff; width in {2,4,8}.  Returns the byte count written (ncols*512*width*2). */

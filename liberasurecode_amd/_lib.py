@@ -55,6 +55,7 @@ def host():
         _proto(h, "ecamd_rs_decode_map", C.c_int, [IP, C.c_int, C.c_int, IP, C.c_int, IP, IP, IP, IP])
         _proto(h, "ecamd_rs_reconstruct_map", C.c_int, [IP, C.c_int, C.c_int, IP, C.c_int, IP, IP, IP])
         _proto(h, "ecamd_rs_check_map", C.c_int, [IP, C.c_int, C.c_int, IP, IP, IP, IP, IP])
+        _proto(h, "ecamd_rs_locate_map", C.c_int, [IP, C.c_int, C.c_int, IP, IP, IP, IP, IP, IP])
         _proto(h, "ecamd_bitslice_eval", C.c_int,
                [IP, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, IP])
         _proto(h, "ecamd_bitslice_source", C.c_int64,
@@ -140,6 +141,14 @@ def dev():
                [C.c_int, C.c_int, C.c_int, VP, C.c_int64, C.c_int64, C.c_int64, C.c_int, VP, VP])
         _proto(d, "ecamd_check_fused_launches", C.c_longlong, [])
         _proto(d, "ecamd_check_prebuild", C.c_int, [C.c_int, C.c_int, VP, C.c_char_p, C.c_char_p])
+        _proto(d, "ecamd_rs_locate", C.c_int,
+               [C.c_int, C.c_int, IP, VP, C.c_int64, C.c_int64, C.c_int64, C.c_int, VP, VP, U32P, VP])
+        _proto(d, "ecamd_xor_locate", C.c_int,
+               [C.c_int, C.c_int, C.c_int, VP, C.c_int64, C.c_int64, C.c_int64, C.c_int, VP, VP, VP])
+        _proto(d, "ecamd_rs_scrub", C.c_int,
+               [C.c_int, C.c_int, VP, C.c_int64, C.c_int64, C.c_int64, C.c_int, VP, VP, IP, IP, IP, VP])
+        _proto(d, "ecamd_locate_fused_launches", C.c_longlong, [])
+        _proto(d, "ecamd_locate_prebuild", C.c_int, [C.c_int, C.c_int, VP, C.c_char_p, C.c_char_p])
         _proto(d, "ecamd_percall_reset", None, [])
         _proto(d, "ecamd_percall_status", C.c_int, [])
         _proto(d, "ecamd_fault_inject", C.c_int, [C.c_char_p, C.c_int])

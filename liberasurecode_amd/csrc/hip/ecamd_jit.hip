@@ -10,7 +10,8 @@
 // launches the LDS-table kernel until the code object is ready, 2 waits for it (tests, bench), 0
 // never uses the bitsliced form; ecamd_bitslice_wait() waits for every compile started so far.
 // The check form (ecamd_rs_check: a syndrome map whose kernel writes status bits, no fragments) is one
-// more entry kind with its own requests and cache keys.
+// more entry kind with its own requests and cache keys, and so is the locate form (ecamd_rs_locate: the
+// check form with a second stage that names the fragment a non-zero syndrome points at).
 #include <hip/hip_runtime.h>
 #include <dirent.h>
 #include <dlfcn.h>
@@ -208,6 +209,7 @@ struct BsEntry {
     int prefetch = 0;         // one-wave form: chunks of the next input loaded ahead (BitsliceStyle::prefetch)
     BsOcc occ;                // one-wave form: amdgpu_waves_per_eu and input barrier (bitslice.hpp)
     bool check = false;       // check form (BitsliceStyle::check): plain maps only
+    bool locate = false;      // locate form (BitsliceStyle::locate_ratio): a check form with a second stage
     int cap_index = 0;    // into kCaps: shared temporaries allowed (fewer: fewer registers)
     std::string arch;     // target of the code object (the requesting device's gcnArchName)
     std::string co_path;  // cache file of the code object
@@ -311,6 +313,12 @@ const std::string& generator_fingerprint()
         const BitsliceNet syn = bitslice_network({3, 1}, 1, 2, 0);
         fp += bitslice_source(syn, 0, chk) + bitslice_source(syn, 2, chk) + bitslice_source(syn, 0, chk_tile) +
               bitslice_source(syn, 2, chk_tile);
+        BitsliceStyle loc = chk, loc_tile = chk_tile;  // the locate form (ecamd_rs_locate), as the check form
+        const std::vector<int> syn2 = {3, 1, 0, 5, 0, 1};
+        loc.locate_ratio = loc_tile.locate_ratio = bitslice_locate_ratio(syn2, 2, 3);
+        const BitsliceNet lsyn = bitslice_network(syn2, 2, 3, 0);
+        fp += bitslice_source(lsyn, 0, loc) + bitslice_source(lsyn, 2, loc) + bitslice_source(lsyn, 0, loc_tile) +
+              bitslice_source(lsyn, 2, loc_tile);
     });
     return fp;
 }
@@ -338,7 +346,7 @@ std::string request_of(const BsEntry& e)
                                 : 0;
     return bitslice_request(e.coeff, e.R, e.K, kCaps[e.cap_index], e.depth, e.copy, e.crc > 0,
                             e.crc > 0 ? (e.crc & 7) : 1, (e.crc & 8) != 0, (e.crc & 16) != 0, e.wave, &e.shifts,
-                            e.prefetch, e.wave || e.occ.threads || cw ? &e.occ : nullptr, cw, e.check);
+                            e.prefetch, e.wave || e.occ.threads || cw ? &e.occ : nullptr, cw, e.check, e.locate);
 }
 std::string object_name(const BsEntry& e)
 {
@@ -452,7 +460,7 @@ void wait_compile(std::unique_lock<std::mutex>& lk, const std::shared_ptr<BsEntr
 // kernels get equal requests.  Returns the key.
 std::vector<int> normalize(const std::vector<int>& coeff, int R, int K, int& depth, bool& copy, int& crc,
                            bool& wave, const std::vector<int>* in_shift, int& prefetch, std::vector<int>& shifts,
-                           BsOcc& occ, bool& check)
+                           BsOcc& occ, bool& check, bool& locate)
 {
     if (crc) {  // position sets 1 / 2 / 4, + 8 for the lane-shift fold, + 16 for nibble piece tables;
         // + 32 for one-wave tiles (with the lane fold, byte tables) in workgroups of (crc >> 6) waves
@@ -461,7 +469,8 @@ std::vector<int> normalize(const std::vector<int>& coeff, int R, int K, int& dep
         crc = (pos >= 4 ? 4 : pos >= 2 ? 2 : 1) | (cw ? 8 | 32 | (cw << 6) | (crc & (1024 | 6144)) : crc & 24);
     }
     copy = copy || crc;
-    check = check && !copy;
+    locate = locate && !copy && R >= 2;
+    check = (check || locate) && !copy;
     wave = wave && !crc;
     // the LDS ring: plain maps, and copy-through maps in one-wave tiles (not the crc variant)
     depth = crc || (copy && !wave) ? 0 : bitslice_depth(depth, K);
@@ -492,7 +501,7 @@ std::vector<int> normalize(const std::vector<int>& coeff, int R, int K, int& dep
         key.push_back(-1);
         key.insert(key.end(), shifts.begin(), shifts.end());
     }
-    if (check) key.push_back(-2);  // (no coefficient or shift is negative)
+    if (check) key.push_back(locate ? -3 : -2);  // (no coefficient or shift is negative)
     return key;
 }
 
@@ -531,7 +540,7 @@ long code_object_scratch(const std::string& code)
 // 0: this form never takes a bitsliced kernel, < 0: the helper is missing or failed.
 int bitslice_prebuild(const std::vector<int>& coeff, int R, int K, int depth, bool copy, int crc, bool wave,
                       const std::vector<int>* in_shift, int prefetch, const BsOcc& occ_in, const std::string& arch,
-                      const std::string& dir, bool check)
+                      const std::string& dir, bool check, bool locate)
 {
     if (R <= 0 || R > kBsMaxR || K <= 0 || K > kBsMaxK) return 0;
     const std::string helper = helper_path();
@@ -539,9 +548,10 @@ int bitslice_prebuild(const std::vector<int>& coeff, int R, int K, int depth, bo
     BsEntry e;
     std::vector<int> shifts;
     BsOcc occ = occ_in;
-    normalize(coeff, R, K, depth, copy, crc, wave, in_shift, prefetch, shifts, occ, check);
+    normalize(coeff, R, K, depth, copy, crc, wave, in_shift, prefetch, shifts, occ, check, locate);
     e.occ = occ;
     e.check = check;
+    e.locate = locate;
     e.coeff = coeff;
     e.R = R;
     e.K = K;
@@ -590,14 +600,15 @@ int bitslice_prebuild(const std::vector<int>& coeff, int R, int K, int depth, bo
 hipFunction_t bitslice_function(int dev, const std::vector<int>& coeff, int R, int K, int depth, bool wait,
                                 std::shared_ptr<void>& hold, bool copy, int crc, bool wave,
                                 const std::vector<int>* in_shift, int prefetch, int* status, const BsOcc* occ_in,
-                                bool check)
+                                bool check, bool locate)
 {
     if (status) *status = -1;
     if (R <= 0 || R > kBsMaxR || K <= 0 || K > kBsMaxK || (helper_path().empty() && shipped_dir().empty()))
         return nullptr;
     std::vector<int> shifts;
     BsOcc occ = occ_in ? *occ_in : BsOcc{};
-    const std::vector<int> key = normalize(coeff, R, K, depth, copy, crc, wave, in_shift, prefetch, shifts, occ, check);
+    const std::vector<int> key = normalize(coeff, R, K, depth, copy, crc, wave, in_shift, prefetch, shifts, occ, check,
+                                           locate);
     std::vector<std::shared_ptr<BsEntry>> evicted;  // released after the lock (declared before it)
     std::unique_lock<std::mutex> lk(g_jit_mu);
     for (size_t i = 0; i < g_running.size();) {  // reap finished compilers, freeing their slots
@@ -629,6 +640,7 @@ hipFunction_t bitslice_function(int dev, const std::vector<int>& coeff, int R, i
         slot->prefetch = prefetch;
         slot->occ = occ;
         slot->check = check;
+        slot->locate = locate;
         slot->arch = device_arch(dev);
         slot->cap_index = first_cap(R, crc, wave);
         start_compile(slot, wait);

@@ -358,14 +358,27 @@ std::string bitslice_source(const BitsliceNet& net, int depth, BitsliceStyle sty
     s << "// generated by liberasurecode_amd bitslice_source: " << net.R << " outputs x " << net.K
       << " inputs, " << net.xor_ops() << " network ops per tile, "
       << (D ? "LDS ring of " + std::to_string(D) + " inputs per wave" : std::string("register loads")) << "\n";
-    const bool check = style.check && !style.crc && !style.copy_through;  // plain maps only
+    // the locate form is a check form (plain maps only) with a second stage; its candidates are the
+    // K - R inputs of A and the R checked rows
+    const int LK = net.K - net.R;
+    const bool locate = !style.locate_ratio.empty() && !style.crc && !style.copy_through && net.R >= 2 && LK >= 1 &&
+                        style.locate_ratio.size() == static_cast<size_t>(net.R - 1) * LK;
+    const bool check = (style.check || locate) && !style.crc && !style.copy_through;  // plain maps only
     if (check) {
-        // the check form's kernarg struct ends with the status words (BsArgs); every other form keeps
-        // the prelude it always had
+        // the check form's kernarg struct ends with the status words (BsArgs), the locate form's with
+        // the suspects after them; every other form keeps the prelude it always had
         std::string pre(kPrelude);
         const std::string tail = "    i32 crc_nfrag;\n};";
-        pre.replace(pre.find(tail), tail.size(), "    i32 crc_nfrag;\n    u32* status;\n    u8 status_bit[8];\n};");
+        pre.replace(pre.find(tail), tail.size(),
+                    locate ? "    i32 crc_nfrag;\n    u32* status;\n    u8 status_bit[8];\n    u32* suspects;\n"
+                             "    u8 frag_bit[32];\n};"
+                           : "    i32 crc_nfrag;\n    u32* status;\n    u8 status_bit[8];\n};");
         s << pre;
+        // the locate form reads its bit numbers through an opaque scalar move inside the (rare) branch
+        // that uses them: the compiler otherwise forms every 1 << bit ahead of the tile loop in VGPRs,
+        // which the 8 x 28 map of (20,8) has none left for (24 bytes of scratch)
+        if (locate)
+            s << "__device__ __forceinline__ u32 opq(u32 x)\n{\n    asm volatile(\"\" : \"+s\"(x));\n    return x;\n}\n";
     } else
         s << kPrelude;
     if (style.crc) s << kPreludeCrc;
@@ -474,7 +487,85 @@ std::string bitslice_source(const BitsliceNet& net, int depth, BitsliceStyle sty
           << "#pragma unroll\n        for (int r = 0; r < " << net.R
           << "; r++)\n#pragma unroll\n            for (int p = 0; p < 16; p++) acc[r][p] = 0u;\n";
     };
+    // the locate form's second stage: the network of ratio's column j on the planes acc[0]
+    const BitsliceNet lnet = locate ? bitslice_network(style.locate_ratio, net.R - 1, LK, kBsLocateCap) : BitsliceNet{};
+    auto locate_stage = [&]() {
+        // stage 1 as the check form: per-row OR and status bit; the ORs are kept for the checked candidates
+        s << "        u32 rowor[" << net.R << "];\n"
+          << "#pragma unroll\n        for (int r = 0; r < " << net.R
+          << "; r++) {\n"
+             "            u32 o = acc[r][0];\n"
+             "#pragma unroll\n"
+             "            for (int p = 1; p < 16; p++) o |= acc[r][p];\n"
+             "            rowor[r] = o;\n"
+             "            if (__builtin_amdgcn_ballot_w64(o != 0u) != 0ull && (threadIdx.x & 63u) == 0u)\n"
+             "                __hip_atomic_fetch_or(a.status + s, 1u << opq(a.status_bit[r]), __ATOMIC_RELAXED, "
+             "__HIP_MEMORY_SCOPE_AGENT);\n"
+             "        }\n"
+             "        u32 dirty = rowor[0];\n"
+             "#pragma unroll\n        for (int r = 1; r < "
+          << net.R
+          << "; r++) dirty |= rowor[r];\n"
+             // wave-uniform: a clean wave is done here
+             "        if (__builtin_amdgcn_ballot_w64(dirty != 0u) != 0ull) {\n"
+             "            u32 keep = 0xffffffffu;\n";
+        // checked candidate c explains the wave's words iff every other row's syndrome is zero
+        for (int c = 0; c < net.R; c++) {
+            s << "            {\n                const u32 bad = 0u";
+            for (int r = 0; r < net.R; r++)
+                if (r != c) s << " | rowor[" << r << "]";
+            s << ";\n                if (__builtin_amdgcn_ballot_w64(bad != 0u) != 0ull) keep &= ~(1u << opq(a.frag_bit[" << LK + c
+              << "]));\n            }\n";
+        }
+        // input candidate j explains them iff S_r == ratio[r][j] * S_0 for every row r >= 1
+        auto lref = [](int v) {
+            char b[24];
+            if (v < 16)
+                std::snprintf(b, sizeof(b), "acc[0][%d]", 15 - v);
+            else
+                std::snprintf(b, sizeof(b), "t%d", v);
+            return std::string(b);
+        };
+        for (int j = 0; j < LK; j++) {
+            const auto& in = lnet.inputs[static_cast<size_t>(j)];
+            s << "            {\n                u32 bad = 0u;\n";
+            std::vector<char> done(in.temps.size(), 0);
+            std::function<void(int)> need = [&](int v) {
+                if (v < 16 || done[static_cast<size_t>(v - 16)]) return;
+                const auto& t = in.temps[static_cast<size_t>(v - 16)];
+                for (int u : t)
+                    if (u >= 0) need(u);
+                done[static_cast<size_t>(v - 16)] = 1;
+                if (t[2] < 0)
+                    s << "                const u32 t" << v << " = x2(" << lref(t[0]) << ", " << lref(t[1]) << ");\n";
+                else
+                    s << "                const u32 t" << v << " = x3(" << lref(t[0]) << ", " << lref(t[1]) << ", "
+                      << lref(t[2]) << ");\n";
+            };
+            for (size_t i = 0; i < in.rows.size(); i++) {
+                const auto& terms = in.rows[i];
+                for (int v : terms) need(v);
+                // the produced plane XORed with the stored syndrome plane of row i / 16 + 1
+                char cur[96];
+                std::snprintf(cur, sizeof(cur), "acc[%zu][%zu]", i / 16 + 1, 15 - i % 16);
+                std::string e(cur);
+                size_t q = 0;
+                for (; q + 1 < terms.size(); q += 2) e = "x3(" + e + ", " + lref(terms[q]) + ", " + lref(terms[q + 1]) + ")";
+                if (q < terms.size()) e = "x2(" + e + ", " + lref(terms[q]) + ")";
+                s << "                bad |= " << e << ";\n";
+            }
+            s << "                if (__builtin_amdgcn_ballot_w64(bad != 0u) != 0ull) keep &= ~(1u << opq(a.frag_bit[" << j
+              << "]));\n            }\n";
+        }
+        s << "            if ((threadIdx.x & 63u) == 0u)\n"
+             "                __hip_atomic_fetch_and(a.suspects + s, keep, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);\n"
+             "        }\n";
+    };
     auto outputs = [&](const char* rout, const char* off) {
+        if (locate) {
+            locate_stage();
+            return;
+        }
         if (check) {
             // acc holds the syndrome planes of [A | I]: all zero on a consistent tile.  The ballot is
             // wave-uniform, so a clean wave skips the atomic altogether; a dirty one sends a single lane.
@@ -1124,7 +1215,7 @@ std::string bitslice_source(const BitsliceNet& net, int depth, BitsliceStyle sty
 std::string bitslice_request(const std::vector<int>& coeff, int R, int K, int cap, int depth, bool copy,
                              bool crc, int crc_pos, bool crc_lane, bool crc_nib, bool wave,
                              const std::vector<int>* in_shift, int prefetch, const BsOcc* occ, int crc_wave,
-                             bool check)
+                             bool check, bool locate)
 {
     std::ostringstream s;
     // flags: bit 0 copy-through, bit 1 crc (which copies too), bits 2-3 log2 of the crc position
@@ -1173,14 +1264,15 @@ std::string bitslice_request(const std::vector<int>& coeff, int R, int K, int ca
     for (size_t i = 0; i < coeff.size(); i++) s << coeff[i] << ((i + 1) % static_cast<size_t>(K) ? " " : "\n");
     // the check form (plain maps only): a trailing word, written only when set, so every other
     // request reads as it always did
-    if (check && !copy && !crc) s << "check\n";
+    // (the locate form -- a check form with a second stage -- says "locate" in its place)
+    if ((check || locate) && !copy && !crc) s << (locate ? "locate\n" : "check\n");
     return s.str();
 }
 
 bool bitslice_parse_request(const std::string& text, std::vector<int>& coeff, int& R, int& K, int& cap,
                             int& depth, bool* copy, bool* crc, int* crc_pos, bool* crc_lane, bool* crc_nib,
                             bool* wave, bool* budget2, std::vector<int>* in_shift, int* prefetch, BsOcc* occ,
-                            int* crc_wave, bool* check)
+                            int* crc_wave, bool* check, bool* locate)
 {
     std::istringstream s(text);
     std::string magic;
@@ -1243,9 +1335,27 @@ bool bitslice_parse_request(const std::string& text, std::vector<int>& coeff, in
         if (!(s >> c) || c < 0 || c > 0xffff) return false;
     std::string word;
     const bool chk = static_cast<bool>(s >> word);
-    if (chk && (word != "check" || (cp & 3))) return false;  // plain maps only
+    if (chk && ((word != "check" && word != "locate") || (cp & 3))) return false;  // plain maps only
+    const bool loc = chk && word == "locate";
+    if (loc && bitslice_locate_ratio(coeff, R, K).empty()) return false;  // >= 2 rows, a non-zero first row
     if (check) *check = chk;
+    if (locate) *locate = loc;
     return true;
+}
+
+std::vector<int> bitslice_locate_ratio(const std::vector<int>& coeff, int R, int K)
+{
+    const int LK = K - R;
+    if (R < 2 || LK < 1 || coeff.size() != static_cast<size_t>(R) * K) return {};
+    const GF16& gf = GF16::get();
+    std::vector<int> ratio(static_cast<size_t>(R - 1) * LK);
+    for (int j = 0; j < LK; j++) {
+        const int a0 = coeff[static_cast<size_t>(j)];
+        if (a0 <= 0 || a0 > 0xffff) return {};
+        for (int r = 1; r < R; r++)
+            ratio[static_cast<size_t>(r - 1) * LK + j] = gf.mul(coeff[static_cast<size_t>(r) * K + j], gf.inv(a0));
+    }
+    return ratio;
 }
 
 }  // namespace ecamd

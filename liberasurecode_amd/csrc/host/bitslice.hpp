@@ -118,7 +118,21 @@ struct BitsliceStyle {
     // accumulator planes, and a wave that sees a non-zero OR has one lane OR bit status_bit[r] into
     // status[stripe] (BsArgs; a global atomic at agent scope).  A consistent stripe causes no write.
     bool check = false;
+    // check form with at least 2 rows (ecamd_rs_locate): the (R - 1) x (K - R) matrix ratio[r - 1][j] =
+    // A[r][j] / A[0][j] of the syndrome map (bitslice_locate_ratio); non-empty selects the locate form.
+    // A wave that sees a non-zero syndrome goes on, in registers: per input candidate j the network of
+    // column j of `ratio` runs on the planes acc[0], every produced plane XORed with the matching plane
+    // of acc[r] and ORed into one register; a checked candidate c takes the OR of every row but its
+    // own.  A candidate survives when no lane of the wave has a bit left, and one lane ANDs the mask
+    // of survivors (bits frag_bit[] of BsArgs; all other bits set) into suspects[stripe].
+    std::vector<int> locate_ratio;
 };
+// ratio[(R - 1) * (K - R)] of the R x K syndrome map [A | I_R] (row-major coeff); empty when R < 2 or
+// an entry of A's first row is zero (no locate form).
+std::vector<int> bitslice_locate_ratio(const std::vector<int>& coeff, int R, int K);
+// Temporaries per candidate of the locate form's second stage (a fixed search setting: the stage runs
+// with the R * 16 syndrome planes live).
+constexpr int kBsLocateCap = 8;
 // LDS words of the CRC image the crc variant reads (host/crc.hpp build_fused_crc_image_pos: byte
 // piece tables per position, chain step 4096 B): npos x 4 x 1024 piece words + gap + 6 butterfly
 // levels + A^1024
@@ -152,13 +166,14 @@ struct BsOcc {
 std::string bitslice_request(const std::vector<int>& coeff, int R, int K, int cap, int depth, bool copy = false,
                              bool crc = false, int crc_pos = 1, bool crc_lane = false, bool crc_nib = false,
                              bool wave = false, const std::vector<int>* in_shift = nullptr, int prefetch = 0,
-                             const BsOcc* occ = nullptr, int crc_wave = 0, bool check = false);
+                             const BsOcc* occ = nullptr, int crc_wave = 0, bool check = false,
+                             bool locate = false);
 bool bitslice_parse_request(const std::string& text, std::vector<int>& coeff, int& R, int& K, int& cap,
                             int& depth, bool* copy = nullptr, bool* crc = nullptr, int* crc_pos = nullptr,
                             bool* crc_lane = nullptr, bool* crc_nib = nullptr, bool* wave = nullptr,
                             bool* budget2 = nullptr, std::vector<int>* in_shift = nullptr,
                             int* prefetch = nullptr, BsOcc* occ = nullptr, int* crc_wave = nullptr,
-                            bool* check = nullptr);
+                            bool* check = nullptr, bool* locate = nullptr);
 
 // Kernel arguments (layout shared by the generated source and the launcher).
 constexpr int kBsTile = 16384;  // bytes of each fragment per workgroup tile (256 lanes x 64 B)
@@ -196,6 +211,11 @@ struct BsArgs {
     // stripe s ORs 1 << status_bit[r] into status[s] when its syndrome is not zero
     uint32_t* status;
     uint8_t status_bit[kBsMaxR];
+    // locate form (BitsliceStyle::locate_ratio; only its generated prelude declares these two): a wave
+    // that sees a non-zero syndrome ANDs into suspects[s] a word with every bit set but those of the
+    // candidates it rules out; frag_bit[i] is the fragment index of input i (the checked rows last)
+    uint32_t* suspects;
+    uint8_t frag_bit[kBsMaxK];
 };
 
 }  // namespace ecamd

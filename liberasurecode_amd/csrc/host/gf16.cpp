@@ -269,4 +269,20 @@ int rs_check_map(const std::vector<int>& G, int k, int m, const std::vector<int>
     return 0;
 }
 
+int rs_locate_map(const std::vector<int>& G, int k, int m, const std::vector<int>& missing,
+                  FragmentMap& out, std::vector<int>& ratio)
+{
+    ratio.clear();
+    if (rs_check_map(G, k, m, missing, out) != 0) return -1;
+    const int R = static_cast<int>(out.outputs.size());
+    const GF16& gf = GF16::get();
+    for (int r = 1; r < R; r++)
+        for (int j = 0; j < k; j++) {
+            const int a0 = out.coeff[static_cast<size_t>(j)];
+            if (a0 == 0) return -1;  // (never for this code: every entry of a check map is non-zero)
+            ratio.push_back(gf.mul(out.coeff[static_cast<size_t>(r) * k + j], gf.inv(a0)));
+        }
+    return 0;
+}
+
 }  // namespace ecamd

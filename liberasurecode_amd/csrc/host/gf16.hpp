@@ -67,6 +67,12 @@ int rs_reconstruct_map(const std::vector<int>& G, int k, int m, const std::vecto
 int rs_check_map(const std::vector<int>& G, int k, int m, const std::vector<int>& missing,
                  FragmentMap& out);
 
+// Locate map (ecamd_rs_locate): the check map, and ratio[(R - 1) * k] with ratio[(r - 1) * k + j] =
+// coeff[r][j] / coeff[0][j] over its R rows (empty for R < 2).  One bad input j makes every word's
+// syndrome S_r = coeff[r][j] * e, so S_r == ratio[r][j] * S_0 names it.  Returns as rs_check_map.
+int rs_locate_map(const std::vector<int>& G, int k, int m, const std::vector<int>& missing,
+                  FragmentMap& out, std::vector<int>& ratio);
+
 // Encode map: inputs 0..k-1, outputs k..k+m-1, generator parity rows.
 FragmentMap rs_encode_map(const std::vector<int>& G, int k, int m);
 

@@ -94,6 +94,28 @@ int ecamd_rs_check_map(const int* G, int k, int m, const int* missing, int* inpu
     return 0;
 }
 
+int ecamd_rs_locate_map(const int* G, int k, int m, const int* missing, int* inputs, int* checked,
+                        int* coeff, int* ncheck, int* ratio)
+{
+    if (!G || k <= 0 || m < 0 || !inputs || !ncheck) return -1;
+    std::vector<int> g(G, G + static_cast<size_t>(k + m) * k);
+    FragmentMap fm;
+    std::vector<int> rt;
+    if (rs_locate_map(g, k, m, minus1_list(missing), fm, rt) != 0) return -1;
+    std::memcpy(inputs, fm.inputs.data(), fm.inputs.size() * sizeof(int));
+    if (!fm.outputs.empty()) {
+        if (!checked || !coeff) return -1;
+        std::memcpy(checked, fm.outputs.data(), fm.outputs.size() * sizeof(int));
+        std::memcpy(coeff, fm.coeff.data(), fm.coeff.size() * sizeof(int));
+    }
+    if (!rt.empty()) {
+        if (!ratio) return -1;
+        std::memcpy(ratio, rt.data(), rt.size() * sizeof(int));
+    }
+    *ncheck = static_cast<int>(fm.outputs.size());
+    return 0;
+}
+
 int ecamd_split_tables(const int* coeff, int R, int K, int row0, int width, int col0, int ncols,
                        uint8_t* out)
 {

@@ -61,9 +61,10 @@ int main(int argc, char** argv)
     int prefetch = 0;
     ecamd::BsOcc occ;
     int crc_wave = 0;
-    bool check = false;
+    bool check = false, locate = false;
     if (!ecamd::bitslice_parse_request(ss.str(), coeff, R, K, cap, depth, &copy, &crc, &crc_pos, &crc_lane,
-                                       &crc_nib, &wave, &budget2, &shifts, &prefetch, &occ, &crc_wave, &check)) {
+                                       &crc_nib, &wave, &budget2, &shifts, &prefetch, &occ, &crc_wave, &check,
+                                       &locate)) {
         std::fprintf(stderr, "ecamd_jitc: bad request %s\n", argv[1]);
         return 2;
     }
@@ -84,6 +85,7 @@ int main(int argc, char** argv)
     style.in_shift = shifts;
     style.prefetch = prefetch;
     style.check = check;
+    if (locate) style.locate_ratio = ecamd::bitslice_locate_ratio(coeff, R, K);
     if (const char* v = std::getenv("ECAMD_BS_WPE")) style.waves = std::atoi(v);  // experiment only
     if (const char* v = std::getenv("ECAMD_BS_WPE_MAX")) style.waves_max = std::atoi(v);  // experiment only
     if (const char* v = std::getenv("ECAMD_BS_LAZY")) style.lazy_temps = std::atoi(v) != 0;

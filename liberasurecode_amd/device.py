@@ -184,6 +184,51 @@ def xor_check(k, m, hd, lay: Layout, stream=None):
         _s(stream)), lay, stream, "xor_check")
 
 
+def _status_suspects(call, lay, stream, what):
+    """Run call(d_status, d_suspects) and return both arrays of nstripes words (waits for `stream`)."""
+    n = max(lay.nstripes, 1)
+    buf = DeviceBuffer(8 * n)
+    try:
+        check(call(buf.ptr, buf.ptr + 4 * n), what)
+        if stream is not None:
+            stream.synchronize()
+        words = buf.download(8 * n).view(np.uint32)
+        return words[:lay.nstripes].copy(), words[n:n + lay.nstripes].copy()
+    finally:
+        buf.free()
+
+
+def rs_locate(k, m, lay: Layout, missing=(), stream=None):
+    """ecamd_rs_locate: (status, suspects, checked_mask).  status as rs_check; suspects[s] is 0 on a
+    consistent stripe, else the mask of fragments that alone explain every disagreement of stripe s:
+    one bit -- located; zero -- more than one fragment is bad.  blocksize must be even."""
+    checked = C.c_uint32(0)
+    status, suspects = _status_suspects(lambda d, u: dev().ecamd_rs_locate(
+        k, m, ints(list(missing) + [-1]), lay.buf.ptr, lay.stripe_stride, lay.frag_stride, lay.blocksize,
+        lay.nstripes, d, u, C.byref(checked), _s(stream)), lay, stream, "rs_locate")
+    return status, suspects, checked.value
+
+
+def xor_locate(k, m, hd, lay: Layout, stream=None):
+    """ecamd_xor_locate: (status, suspects) of full flat_xor_hd stripes."""
+    return _status_suspects(lambda d, u: dev().ecamd_xor_locate(
+        k, m, hd, lay.buf.ptr, lay.stripe_stride, lay.frag_stride, lay.blocksize, lay.nstripes, d, u,
+        _s(stream)), lay, stream, "xor_locate")
+
+
+def rs_scrub(k, m, lay: Layout, stream=None):
+    """ecamd_rs_scrub on full stripes (m >= 2): locate, then repair in place every stripe with exactly
+    one suspect.  Returns (status, suspects, (n_clean, n_repaired, n_unlocated)); waits for `stream`, so
+    the repairs are complete on return."""
+    counts = [C.c_int(0), C.c_int(0), C.c_int(0)]
+    status, suspects = _status_suspects(lambda d, u: dev().ecamd_rs_scrub(
+        k, m, lay.buf.ptr, lay.stripe_stride, lay.frag_stride, lay.blocksize, lay.nstripes, d, u,
+        C.byref(counts[0]), C.byref(counts[1]), C.byref(counts[2]), _s(stream)), lay, stream, "rs_scrub")
+    if stream is None:
+        check(dev().ecamd_synchronize(), "synchronize")
+    return status, suspects, tuple(c.value for c in counts)
+
+
 class GF16Map:
     """An arbitrary R x K GF(2^16) fragment map prepared on the device."""
 

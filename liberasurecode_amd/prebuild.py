@@ -72,6 +72,11 @@ def all_ops(full=None):
 # ecamd_bitslice_prebuild's operations only.  (4, 2)'s check takes no bitsliced form and builds nothing.
 CHECK_OPS = [(10, 4, []), (4, 2, []), (20, 8, [])] + [(10, 4, [f]) for f in range(14)]
 
+# (k, m, missing): the fused kernels of ecamd_rs_locate (ecamd_locate_prebuild), for the patterns of
+# CHECK_OPS: a scrub of full stripes (ecamd_rs_scrub) and the guard that names the survivor to drop.
+# Again a list of its own; (4, 2) builds nothing.
+LOCATE_OPS = [(10, 4, []), (4, 2, []), (20, 8, [])] + [(10, 4, [f]) for f in range(14)]
+
 # (backend, k, m, hd): the CHKSUM_CRC32 framed encode's codec-and-checksum kernel, one per code whatever
 # the object size -- Swift's default rs_vand (10, 4) (whole objects and 1 MiB segments alike), the
 # other BASELINE codes, and flat_xor_hd (3, 3, 3)
@@ -90,6 +95,8 @@ def prebuild(arch="gfx950", jobs=8, verbose=False, full=None):
     lib.ecamd_frame_prebuild.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_char_p]
     lib.ecamd_check_prebuild.restype = C.c_int
     lib.ecamd_check_prebuild.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_char_p, C.c_char_p]
+    lib.ecamd_locate_prebuild.restype = C.c_int
+    lib.ecamd_locate_prebuild.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_char_p, C.c_char_p]
     lib.ecamd_last_error.restype = C.c_char_p
     os.makedirs(JIT_DIR, exist_ok=True)
     for name in os.listdir(JIT_DIR):  # objects of an earlier generator or knob set are never looked up
@@ -105,6 +112,9 @@ def prebuild(arch="gfx950", jobs=8, verbose=False, full=None):
         if op[0] == "check":
             _, k, m, miss = op
             return op, lib.ecamd_check_prebuild(k, m, C.cast(_ints(miss), C.c_void_p), arch.encode(), JIT_DIR.encode())
+        if op[0] == "locate":
+            _, k, m, miss = op
+            return op, lib.ecamd_locate_prebuild(k, m, C.cast(_ints(miss), C.c_void_p), arch.encode(), JIT_DIR.encode())
         k, m, miss, dest, rebuild = op
         arr = _ints(miss) if miss is not None else None
         rc = lib.ecamd_bitslice_prebuild(k, m, C.cast(arr, C.c_void_p) if arr is not None else None, dest, rebuild,
@@ -113,7 +123,8 @@ def prebuild(arch="gfx950", jobs=8, verbose=False, full=None):
 
     with ThreadPoolExecutor(max_workers=max(1, jobs)) as ex:
         results = list(ex.map(one, all_ops(full) + [("frame",) + c for c in FRAME_CODES] +
-                              [("check",) + tuple(c) for c in CHECK_OPS]))
+                              [("check",) + tuple(c) for c in CHECK_OPS] +
+                              [("locate",) + tuple(c) for c in LOCATE_OPS]))
     bad = [(op, rc) for op, rc in results if rc < 0]
     if verbose:
         for op, rc in results:

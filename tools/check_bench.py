@@ -8,7 +8,14 @@ bitslice 0; C3 only) -- each repetition the mean of `--n` back-to-back calls.  (
 `--per-cu LIST` repeats (b) with knob check_per_cu at each value (resident one-wave workgroups per
 CU; -1 the default policy).  `--parent-encode-ms X` records the yardstick: the encode pass time of a
 bench.py run of the parent commit in the same session.  One JSON document on stdout, also written to
-`--out`."""
+`--out`.
+
+`--locate` measures ecamd_rs_locate instead (C3 only): alternating repetitions of (a) the fused check and
+the fused locate on a clean batch -- the same loads and network; locate adds one memset and the finalize
+launch -- and (b) both on an all-dirty batch, fragment 3 of every stripe rewritten with other data so
+that every wave of every tile takes the second stage.  The VGPR and scratch figures of the shipped
+(10,4) and (20,8) locate objects are read from freshly built code objects when llvm-readelf is there.
+`--parent-check-ms X` records the parent commit's fused check time of the same session."""
 import argparse
 import json
 import os
@@ -95,8 +102,80 @@ def run(d, st, k, m, F, S, reps, n, generic, per_cu):
     return out
 
 
+def object_figures(d, k, m):
+    """VGPRs, scratch bytes and size of the locate code object of (k, m), built into a temporary directory."""
+    import re
+    import subprocess
+    import tempfile
+    readelf = "/opt/rocm/lib/llvm/bin/llvm-readelf"
+    with tempfile.TemporaryDirectory() as tmp:
+        if d.ecamd_locate_prebuild(k, m, None, b"gfx950", tmp.encode()) != 1 or not os.path.exists(readelf):
+            return None
+        co = [n for n in os.listdir(tmp) if n.endswith(".co")][0]
+        notes = subprocess.run([readelf, "--notes", os.path.join(tmp, co)], capture_output=True, text=True).stdout
+        fig = {key: int(re.search(r"\." + key + r":\s+(\d+)", notes).group(1))
+               for key in ("vgpr_count", "sgpr_count", "private_segment_fixed_size", "vgpr_spill_count")}
+        fig["object_bytes"] = os.path.getsize(os.path.join(tmp, co))
+        return fig
+
+
+def run_locate(d, st, reps, n):
+    k, m, F, S = 10, 4, 1 << 20, 256
+    lay = D.Layout.alloc(k + m, F, S)
+    lay.fill_splitmix(nfrags=k, stream=st)
+    words = D.DeviceBuffer(8 * S)
+    checked = _lib.u32s([0])
+    args = (lay.buf.ptr, lay.stripe_stride, lay.frag_stride, F, S)
+
+    def check():
+        _lib.check(d.ecamd_rs_check(k, m, None, *args, words.ptr, checked, st.handle), "rs_check")
+
+    def locate():
+        _lib.check(d.ecamd_rs_locate(k, m, None, *args, words.ptr, words.ptr + 4 * S, checked, st.handle), "rs_locate")
+
+    d.ecamd_tune(b"bitslice", 2)
+    D.rs_encode(k, m, lay, stream=st)
+    n0 = d.ecamd_locate_fused_launches()
+    locate()
+    st.synchronize()
+    fused_launches = d.ecamd_locate_fused_launches() - n0
+    assert fused_launches > 0, "the fused locate kernel did not run"
+    assert not words.download().any(), "encoded stripes must read clean"
+    for _ in range(60):  # settle the clocks
+        check()
+    st.synchronize()
+    algo = S * (k + m) * F
+    ms = {"check_clean": [], "locate_clean": [], "check_dirty": [], "locate_dirty": []}
+    for _ in range(reps):
+        ms["check_clean"].append(timed(st, check, n))
+        ms["locate_clean"].append(timed(st, locate, n))
+    # all-dirty: fragment 3 of every stripe holds other data, so every word of every tile disagrees
+    _lib.check(d.ecamd_fill_splitmix(lay.buf.ptr + 3 * lay.frag_stride, lay.stripe_stride, lay.frag_stride, 1, F, S, 0,
+                                     0x5EED, st.handle), "fill")
+    locate()
+    st.synchronize()
+    got = words.download().view("uint32")
+    assert (got[:S] == 0xF << k).all() and (got[S:] == 1 << 3).all(), "every stripe must name fragment 3"
+    for _ in range(reps):
+        ms["check_dirty"].append(timed(st, check, n))
+        ms["locate_dirty"].append(timed(st, locate, n))
+    out = {"k": k, "m": m, "fragment_bytes": F, "stripes": S, "algorithmic_bytes": algo,
+           "fused_launches_per_call": fused_launches}
+    out.update({name: series(v, algo) for name, v in ms.items()})
+    c, l = out["check_clean"], out["locate_clean"]
+    out["clean_locate_minus_check_ms"] = round(l["mean_ms"] - c["mean_ms"], 4)
+    out["clean_within_check_spread"] = bool(l["mean_ms"] <= c["max_ms"])
+    out["dirty_locate_over_clean_locate"] = round(out["locate_dirty"]["mean_ms"] / l["mean_ms"], 4)
+    out["objects"] = {"10,4": object_figures(d, 10, 4), "20,8": object_figures(d, 20, 8)}
+    lay.buf.free()
+    words.free()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--locate", action="store_true", help="measure ecamd_rs_locate at C3 instead")
+    ap.add_argument("--parent-check-ms", type=float, default=None)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--n", type=int, default=20)
     ap.add_argument("--per-cu", default="", help="comma-separated check_per_cu values to A/B at C3")
@@ -108,6 +187,18 @@ def main():
     d = _lib.dev()
     st = D.Stream()
     per_cu = [int(x) for x in a.per_cu.split(",") if x.strip()]
+    if a.locate:
+        doc = {"tool": "tools/check_bench.py --locate", "reps": a.reps, "calls_per_rep": a.n,
+               "c3": run_locate(d, st, a.reps, a.n)}
+        if a.parent_check_ms is not None:
+            doc["yardstick"] = {"parent_check_fused_ms": a.parent_check_ms}
+        d.ecamd_tune(b"bitslice", 1)
+        text = json.dumps(doc, indent=1)
+        print(text)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write(text + "\n")
+        return
     doc = {"tool": "tools/check_bench.py", "reps": a.reps, "calls_per_rep": a.n,
            "c3": run(d, st, 10, 4, 1 << 20, 256, a.reps, a.n, True, per_cu)}
     if not a.no_c5:
