@@ -1,0 +1,521 @@
+// ecamd_check.hip -- stripe consistency check, locate and scrub (ecamd_rs_check / ecamd_xor_check,
+// ecamd_rs_locate / ecamd_xor_locate, ecamd_rs_scrub; DESIGN.md "Consistency check", "Locate and scrub").
+//
+// d_status[s]: the checked fragments of stripe s that disagree with its inputs.  d_suspects[s]
+// (locate): the fragments that ALONE explain every disagreement of stripe s.
+//
+// Fused stage (rs_vand, whole bitsliced tiles; ecamd::check_fused in ecamd_device.hip): the check
+// form of the bitsliced kernel over the syndrome map [A | I] reads the K inputs and the R checked
+// fragments and writes only the status bits of inconsistent stripes; its locate form also ANDs the
+// candidates it rules out away from the suspects.  Generic stage (everything else: tails, small
+// fragments, shapes the bitsliced kernel declines, maps still compiling, knob bitslice 0, flat XOR):
+// the strided applies compute the expected fragments into the stream context's scratch (slot
+// kCheckScratchSlot, at most kCheckScratchBytes, so long batches go stripe chunk by stripe chunk and
+// long fragments byte range by byte range) and check_compare_kernel / locate_compare_kernel compare
+// them with the stored ones.  Both stages OR into the same status words and AND into the same
+// suspects, which run_check sets first; locate_finalize_kernel masks the suspects with the
+// participating fragments and clears them on clean stripes -- all on the caller's stream, in order.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <memory>
+#include <vector>
+
+#include "../host/gf16.hpp"
+#include "ecamd.h"
+#include "ecamd_host.h"
+#include "ecamd_internal.hpp"
+
+using namespace ecamd;
+
+namespace {
+
+#define HIP_TRY(expr)                                                                      \
+    do {                                                                                   \
+        hipError_t e_ = (expr);                                                            \
+        if (e_ != hipSuccess)                                                              \
+            return dev_fail(ECAMD_EHIP, "%s: %s", #expr, hipGetErrorString(e_));           \
+    } while (0)
+
+struct CheckCmpArgs {
+    const uint8_t* base;  // stored: row r of stripe s at base + s*stripe_stride + off[r]
+    const uint8_t* calc;  // computed: row r of stripe s at calc + (s*nrows + r)*pitch
+    uint32_t* status;     // of the launch's first stripe
+    int64_t stripe_stride;
+    int64_t pitch;
+    int64_t len;          // bytes compared per fragment
+    int64_t off[32];
+    uint8_t bit[32];
+    int nrows;
+};
+
+// grid (x, row, stripe): 16-byte pieces of exactly `len` bytes, the last piece masked to the
+// fragment's own bytes (read byte by byte, so nothing past `len` is ever touched); one atomicOr per
+// (wave, row) that differs, none for a wave that sees no difference.
+__global__ void __launch_bounds__(256) check_compare_kernel(CheckCmpArgs a)
+{
+    const int r = blockIdx.y;
+    const int64_t s = blockIdx.z;
+    const uint8_t* x = a.base + s * a.stripe_stride + a.off[r];
+    const uint8_t* y = a.calc + (s * a.nrows + r) * a.pitch;
+    const int64_t whole = a.len >> 4;
+    uint32_t d = 0;
+    for (int64_t p = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x; p < whole;
+         p += static_cast<int64_t>(gridDim.x) * 256) {
+        const uint4 u = *reinterpret_cast<const uint4*>(x + p * 16);
+        const uint4 v = *reinterpret_cast<const uint4*>(y + p * 16);
+        d |= (u.x ^ v.x) | (u.y ^ v.y) | (u.z ^ v.z) | (u.w ^ v.w);
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+        for (int64_t i = whole << 4; i < a.len; i++) d |= static_cast<uint32_t>(x[i] ^ y[i]);
+    if (__ballot(d != 0u) != 0ull && (threadIdx.x & 63u) == 0u) atomicOr(a.status + s, 1u << a.bit[r]);
+}
+
+// Locate, generic stage: the compare step also names the single fragment that explains a stripe's
+// disagreements.  The R x K map A (R checked rows over K inputs) comes as rat[r*K + j] =
+// A[r][j] / A[piv[j]][j], piv[j] the first row with A[r][j] != 0 and colmask[j] the rows where it is
+// non-zero (rs_vand: every row, piv 0; flat XOR: the parity bitmaps, all ratios 1).  R * K <= 256
+// because K + R <= 32.
+constexpr int kLocMaxRK = 256;
+struct LocateCmpArgs {
+    const uint8_t* base;  // as CheckCmpArgs
+    const uint8_t* calc;
+    uint32_t* status;
+    uint32_t* suspects;  // of the launch's first stripe
+    int64_t stripe_stride;
+    int64_t pitch;
+    int64_t len;
+    int64_t off[32];
+    uint32_t colmask[32];
+    uint16_t rat[kLocMaxRK];
+    uint8_t piv[32];
+    uint8_t row_bit[32];  // fragment index of checked row r
+    uint8_t in_bit[32];   // fragment index of input j
+    int nrows, ncols;
+};
+
+// c times both 16-bit words of x in GF(2^16), polynomial 0x1100b: shift and xor, no table.
+__device__ __forceinline__ uint32_t gf16_mul2(uint32_t c, uint32_t x)
+{
+    uint32_t acc = 0;
+#pragma unroll
+    for (int b = 0; b < 16; b++) {
+        if ((c >> b) & 1u) acc ^= x;
+        const uint32_t hi = x & 0x80008000u;
+        x = ((x & 0x7fff7fffu) << 1) ^ ((hi >> 15) * 0x100bu);
+    }
+    return acc;
+}
+
+// Syndrome piece p (16 bytes) of one row: stored ^ computed; the last, partial piece byte by byte
+// and zero-padded, so nothing past `len` is ever read.
+__device__ __forceinline__ uint4 locate_piece(const uint8_t* x, const uint8_t* y, int64_t p, int64_t whole, int64_t len)
+{
+    if (p < whole) {
+        const uint4 u = *reinterpret_cast<const uint4*>(x + p * 16);
+        const uint4 v = *reinterpret_cast<const uint4*>(y + p * 16);
+        return uint4{u.x ^ v.x, u.y ^ v.y, u.z ^ v.z, u.w ^ v.w};
+    }
+    uint32_t w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int i = 0; i < 16; i++) {
+        const int64_t q = (whole << 4) + i;
+        const uint32_t d = q < len ? static_cast<uint32_t>(x[q] ^ y[q]) : 0u;
+        w[i >> 2] |= d << (8 * (i & 3));
+    }
+    return uint4{w[0], w[1], w[2], w[3]};
+}
+
+// grid (x, stripe): one thread takes all R rows of a 16-byte piece.  Status bits as
+// check_compare_kernel.  For a dirty piece only: checked candidate c survives iff row c alone is
+// non-zero; input candidate j survives iff exactly the rows of colmask[j] are non-zero and
+// S_r == rat[r][j] * S_piv for each of them.  A dirty wave issues one atomicOr and one atomicAnd.
+__global__ void __launch_bounds__(256) locate_compare_kernel(LocateCmpArgs a)
+{
+    const int64_t s = blockIdx.y;
+    const uint8_t* xs = a.base + s * a.stripe_stride;
+    const uint8_t* ys = a.calc + s * a.nrows * a.pitch;
+    const int64_t whole = a.len >> 4, pieces = (a.len + 15) >> 4;
+    uint32_t st = 0u, keep = 0xffffffffu;
+    for (int64_t p = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x; p < pieces;
+         p += static_cast<int64_t>(gridDim.x) * 256) {
+        uint32_t nz = 0u;
+        for (int r = 0; r < a.nrows; r++) {
+            const uint4 d = locate_piece(xs + a.off[r], ys + r * a.pitch, p, whole, a.len);
+            if ((d.x | d.y | d.z | d.w) != 0u) nz |= 1u << r;
+        }
+        if (nz == 0u) continue;
+        for (int r = 0; r < a.nrows; r++) {
+            if ((nz >> r) & 1u) st |= 1u << a.row_bit[r];
+            if (nz != (1u << r)) keep &= ~(1u << a.row_bit[r]);
+        }
+        for (int j = 0; j < a.ncols; j++) {
+            bool ok = nz == a.colmask[j];
+            if (ok) {
+                const int pv = a.piv[j];
+                const uint4 s0 = locate_piece(xs + a.off[pv], ys + pv * a.pitch, p, whole, a.len);
+                for (int r = 0; r < a.nrows && ok; r++) {
+                    if (r == pv || !((nz >> r) & 1u)) continue;
+                    const uint32_t c = a.rat[r * a.ncols + j];
+                    const uint4 d = locate_piece(xs + a.off[r], ys + r * a.pitch, p, whole, a.len);
+                    ok = gf16_mul2(c, s0.x) == d.x && gf16_mul2(c, s0.y) == d.y && gf16_mul2(c, s0.z) == d.z &&
+                         gf16_mul2(c, s0.w) == d.w;
+                }
+            }
+            if (!ok) keep &= ~(1u << a.in_bit[j]);
+        }
+    }
+    for (int o = 32; o; o >>= 1) {
+        st |= __shfl_xor(st, o);
+        keep &= __shfl_xor(keep, o);
+    }
+    if ((threadIdx.x & 63u) == 0u && st != 0u) {
+        atomicOr(a.status + s, st);
+        atomicAnd(a.suspects + s, keep);
+    }
+}
+
+// suspects[s] = status[s] ? suspects[s] & participating : 0 (the last step of a locate call).
+__global__ void __launch_bounds__(256) locate_finalize_kernel(const uint32_t* status, uint32_t* suspects,
+                                                              uint32_t participating, int n)
+{
+    const int s = static_cast<int>(blockIdx.x) * 256 + static_cast<int>(threadIdx.x);
+    if (s < n) suspects[s] = status[s] ? suspects[s] & participating : 0u;
+}
+
+// What the entry points differ in.  Fragment f of stripe s lies at base + s*stripe_stride +
+// f*frag_stride.
+struct CheckPlan {
+    std::vector<int> inputs, checked;     // fragment indices of the K inputs and the R checked fragments
+    const std::vector<int>* A = nullptr;  // R x K over GF(2^16): checked row r = sum of A[r][j] * input j
+    // what computes the checked rows into the scratch
+    const ecamd_map* map = nullptr;  // rs_vand: ecamd_map_apply_strided; whole tiles take the fused stage
+    std::vector<uint32_t> masks;     // flat XOR: ecamd_xor_apply_strided over the parity bitmaps; never fused
+    CheckMap cached;                 // what A and map point into: the cached check map (rs_vand)
+    std::vector<int> bitmaps;        // or the parity bitmaps as 0 / 1 (flat XOR)
+};
+
+// Bytes [from, bs) of the checked fragments at off[] (bit bits[r] each) of every stripe against what
+// the plan's apply computes from the inputs at in_off[].  `from` a multiple of 16.  With `loc` (its
+// map tables, input bits and suspects filled in) the compare step is locate_compare_kernel, which
+// writes the status bits too.
+int check_generic(int dev, void* stream, const CheckPlan& p, const uint8_t* base, int64_t stripe_stride,
+                  const int64_t* in_off, const int64_t* off, const uint8_t* bits, int64_t from, int64_t bs, int nstripes,
+                  uint32_t* d_status, const LocateCmpArgs* loc)
+{
+    const int nrows = static_cast<int>(p.checked.size());
+    if (from >= bs || nrows <= 0 || nstripes <= 0) return 0;
+    if (nrows > 32) return dev_fail(ECAMD_EINVAL, "check of %d fragments", nrows);
+    const auto st = static_cast<hipStream_t>(stream);
+    const int64_t cap = static_cast<int64_t>(kCheckScratchBytes);
+    const int64_t seg = std::max<int64_t>(65536, cap / nrows / 65536 * 65536);  // fragment bytes per pass
+    for (int64_t f0 = from; f0 < bs; f0 += seg) {
+        const int64_t len = std::min(seg, bs - f0);
+        const int64_t pitch = (len + 255) & ~int64_t(255);
+        const int per = static_cast<int>(std::min<int64_t>(std::clamp<int64_t>(cap / (pitch * nrows), 1, 65535), nstripes));
+        uint32_t* scratch = nullptr;
+        int rc = stream_scratch(dev, stream, kCheckScratchSlot, static_cast<size_t>(per) * nrows * pitch / 4, &scratch);
+        if (rc) return rc;
+        auto* calc = reinterpret_cast<uint8_t*>(scratch);
+        std::vector<int64_t> io(in_off, in_off + p.inputs.size()), oo;
+        for (auto& v : io) v += f0;
+        for (int r = 0; r < nrows; r++) oo.push_back(r * pitch);
+        for (int s0 = 0; s0 < nstripes; s0 += per) {
+            const int ns = std::min(per, nstripes - s0);
+            const uint8_t* in = base + s0 * stripe_stride;
+            rc = p.map ? ecamd_map_apply_strided(p.map, in, stripe_stride, io.data(), calc, nrows * pitch, oo.data(), len, ns, stream)
+                       : ecamd_xor_apply_strided(p.masks.data(), nrows, static_cast<int>(io.size()), in, stripe_stride, io.data(),
+                                                 calc, nrows * pitch, oo.data(), len, ns, stream);
+            if (rc) return rc;
+            // the fields both compare kernels take
+            auto common = [&](auto& a, uint8_t* row_bit) {
+                a.base = base + s0 * stripe_stride + f0;
+                a.calc = calc;
+                a.status = d_status + s0;
+                a.stripe_stride = stripe_stride;
+                a.pitch = pitch;
+                a.len = len;
+                a.nrows = nrows;
+                for (int r = 0; r < nrows; r++) {
+                    a.off[r] = off[r];
+                    row_bit[r] = bits[r];
+                }
+            };
+            if (loc) {
+                LocateCmpArgs l = *loc;
+                common(l, l.row_bit);
+                l.suspects = loc->suspects + s0;
+                const unsigned lx = static_cast<unsigned>(std::clamp<int64_t>((((len + 15) >> 4) + 1023) / 1024, 1, 1024));
+                hipLaunchKernelGGL(locate_compare_kernel, dim3(lx, static_cast<unsigned>(ns)), dim3(256), 0, st, l);
+            } else {
+                CheckCmpArgs c{};
+                common(c, c.bit);
+                const unsigned gx = static_cast<unsigned>(std::clamp<int64_t>(((len >> 4) + 1023) / 1024, 1, 1024));
+                hipLaunchKernelGGL(check_compare_kernel, dim3(gx, static_cast<unsigned>(nrows), static_cast<unsigned>(ns)),
+                                   dim3(256), 0, st, c);
+            }
+            HIP_TRY(hipGetLastError());
+        }
+    }
+    return 0;
+}
+
+// The layout checks of every entry point and, for a locate, its own two.
+int check_layout(bool locate, const void* base, int64_t stripe_stride, int64_t frag_stride, int64_t blocksize,
+                 int nstripes, const uint32_t* d_status, const uint32_t* d_suspects)
+{
+    if (!base || !d_status || nstripes < 0 || blocksize < 1 || frag_stride < blocksize)
+        return dev_fail(ECAMD_EINVAL, "bad base / status / blocksize / strides");
+    if ((reinterpret_cast<uintptr_t>(base) & 15u) || stripe_stride % 16 || frag_stride % 16)
+        return dev_fail(ECAMD_EINVAL, "fragment addresses must be 16-byte aligned");
+    if (locate && !d_suspects) return dev_fail(ECAMD_EINVAL, "null suspects");
+    // an odd size ends in half a word, whose product is cut to 8 bits: proportionality cannot be tested
+    if (locate && (blocksize & 1))
+        return dev_fail(ECAMD_EINVAL, "locate needs an even blocksize (%lld)", static_cast<long long>(blocksize));
+    return 0;
+}
+
+// The map tables of LocateCmpArgs for the R x K matrix A (row-major; entries 0..0xffff).  The ratio
+// matrix is also computed by rs_locate_map (host planning) and bitslice_locate_ratio (the generated
+// kernel); this one stays apart because it alone takes a column's FIRST NON-ZERO row as the pivot and
+// masks the rows where the column is zero -- the flat XOR bitmaps have zeros, an rs_vand map has none.
+void locate_tables(const std::vector<int>& A, int R, int K, LocateCmpArgs& l)
+{
+    const GF16& gf = GF16::get();
+    l.nrows = R;
+    l.ncols = K;
+    for (int j = 0; j < K; j++) {
+        int pv = -1;
+        uint32_t mask = 0;
+        for (int r = 0; r < R; r++)
+            if (A[static_cast<size_t>(r) * K + j]) {
+                if (pv < 0) pv = r;
+                mask |= 1u << r;
+            }
+        l.piv[j] = static_cast<uint8_t>(std::max(pv, 0));
+        l.colmask[j] = mask;
+        for (int r = 0; r < R; r++)
+            l.rat[r * K + j] = pv < 0 ? 0 : static_cast<uint16_t>(gf.mul(A[static_cast<size_t>(r) * K + j],
+                                                                         gf.inv(A[static_cast<size_t>(pv) * K + j])));
+    }
+}
+
+// The check (d_suspects null) or locate of one validated call: both arrays set, the fused stage over
+// whole tiles, the generic stage over the rest, the finalize step of a locate.  StreamUse: the scratch
+// of the stream context outlives the call.
+int run_check(int dev, const CheckPlan& p, const void* base, int64_t stripe_stride, int64_t frag_stride,
+              int64_t blocksize, int nstripes, uint32_t* d_status, uint32_t* d_suspects, void* stream)
+{
+    if (nstripes == 0) return 0;
+    const StreamUse use(dev, stream);
+    const auto st = static_cast<hipStream_t>(stream);
+    const size_t words = static_cast<size_t>(nstripes) * sizeof(uint32_t);
+    if (d_suspects) HIP_TRY(hipMemsetAsync(d_suspects, 0xff, words, st));
+    HIP_TRY(hipMemsetAsync(d_status, 0, words, st));
+    const int K = static_cast<int>(p.inputs.size()), R = static_cast<int>(p.checked.size());
+    const auto* b = static_cast<const uint8_t*>(base);
+    std::vector<int64_t> in_off, chk_off;
+    std::vector<uint8_t> in_bits, bits;
+    uint32_t participating = 0;
+    for (int i : p.inputs) {
+        in_off.push_back(i * frag_stride);
+        in_bits.push_back(static_cast<uint8_t>(i));
+        participating |= 1u << i;
+    }
+    for (int f : p.checked) {
+        chk_off.push_back(f * frag_stride);
+        bits.push_back(static_cast<uint8_t>(f));
+        participating |= 1u << f;
+    }
+    // fewer than 2 checked fragments tell nothing apart: the check, then every participating
+    // fragment of a dirty stripe
+    const bool locating = d_suspects && R >= 2;
+    auto fused = [&](int row0, int nrows) {
+        return check_fused(dev, *p.A, K, row0, nrows, b, stripe_stride, in_off.data(), chk_off.data(), bits.data(), d_status,
+                           locating ? d_suspects : nullptr, in_bits.data(), blocksize, nstripes, stream);
+    };
+    // whole tiles through the fused kernel; what it covered is done, the rest of each fragment goes
+    // the generic way
+    int64_t cover = 0;
+    if (p.map && locating) {
+        // one launch over all R rows: the second stage needs every row's syndrome in one wave, so
+        // more than 8 rows are declined and take the generic stage alone
+        cover = fused(0, R);
+    } else if (p.map) {
+        // one launch per group of 8 rows; only what EVERY group covered is done
+        cover = blocksize;
+        for (int row0 = 0; row0 < R && cover >= 0; row0 += 8) cover = std::min(cover, fused(row0, std::min(8, R - row0)));
+    }
+    if (cover < 0) return static_cast<int>(cover);
+    LocateCmpArgs loc{};
+    if (locating) {
+        loc.suspects = d_suspects;
+        locate_tables(*p.A, R, K, loc);
+        for (int j = 0; j < K; j++) loc.in_bit[j] = in_bits[static_cast<size_t>(j)];
+    }
+    const int rc = check_generic(dev, stream, p, b, stripe_stride, in_off.data(), chk_off.data(), bits.data(), cover,
+                                 blocksize, nstripes, d_status, locating ? &loc : nullptr);
+    if (rc || !d_suspects) return rc;
+    hipLaunchKernelGGL(locate_finalize_kernel, dim3(static_cast<unsigned>((nstripes + 255) / 256)), dim3(256), 0, st,
+                       d_status, d_suspects, participating, nstripes);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// ecamd_rs_check (locate false) and ecamd_rs_locate: a bad layout is reported before too many missing
+// fragments, so it is checked before the plan is made.
+int rs_call(bool locate, int k, int m, const int* missing, const void* base, int64_t stripe_stride, int64_t frag_stride,
+            int64_t blocksize, int nstripes, uint32_t* d_status, uint32_t* d_suspects, uint32_t* checked, void* stream)
+{
+    int dev = 0;
+    int rc = dev_ensure(&dev);
+    if (rc) return rc;
+    if (k <= 0 || m < 0 || k + m > 32)
+        return dev_fail(ECAMD_EINVAL, "%s needs k + m <= 32 (k=%d m=%d)", locate ? "locate" : "check", k, m);
+    if ((rc = check_layout(locate, base, stripe_stride, frag_stride, blocksize, nstripes, d_status, d_suspects))) return rc;
+    CheckPlan p;
+    if ((rc = check_map(k, m, missing, p.cached))) return rc;
+    p.inputs = *p.cached.inputs;
+    p.checked = *p.cached.checked;
+    p.A = p.cached.coeff;
+    p.map = p.cached.map;
+    uint32_t mask = 0;
+    for (int f : p.checked) mask |= 1u << f;
+    if (checked) *checked = mask;  // for an empty batch too
+    return run_check(dev, p, base, stripe_stride, frag_stride, blocksize, nstripes, d_status, locate ? d_suspects : nullptr,
+                     stream);
+}
+
+// ecamd_xor_check (locate false) and ecamd_xor_locate: the parity bitmaps as a 0 / 1 map over GF(2^16).
+int xor_call(bool locate, int k, int m, int hd, const void* base, int64_t stripe_stride, int64_t frag_stride,
+             int64_t blocksize, int nstripes, uint32_t* d_status, uint32_t* d_suspects, void* stream)
+{
+    int dev = 0;
+    int rc = dev_ensure(&dev);
+    if (rc) return rc;
+    unsigned pb[32], db[32];
+    if (k <= 0 || m <= 0 || k + m > 32 || ecamd_xor_code_tables(k, m, hd, pb, db) != 0)
+        return dev_fail(ECAMD_EINVAL, "not a flat_xor_hd code: k=%d m=%d hd=%d", k, m, hd);
+    if ((rc = check_layout(locate, base, stripe_stride, frag_stride, blocksize, nstripes, d_status, d_suspects))) return rc;
+    CheckPlan p;
+    p.masks.assign(pb, pb + m);
+    for (int j = 0; j < k; j++) p.inputs.push_back(j);
+    for (int r = 0; r < m; r++) {
+        p.checked.push_back(k + r);
+        for (int j = 0; j < k; j++) p.bitmaps.push_back((pb[r] >> j) & 1u);
+    }
+    p.A = &p.bitmaps;
+    return run_check(dev, p, base, stripe_stride, frag_stride, blocksize, nstripes, d_status, locate ? d_suspects : nullptr,
+                     stream);
+}
+
+// The check map of (k, m, missing) planned on the host alone (build time: no device).
+int prebuild_plan(const char* what, int k, int m, const int* missing, const char* arch, const char* dir, FragmentMap& fm)
+{
+    if (!arch || !dir) return dev_fail(ECAMD_EINVAL, "null arch / dir");
+    if (k <= 0 || m < 0 || k + m > 32) return dev_fail(ECAMD_EINVAL, "%s needs k + m <= 32 (k=%d m=%d)", what, k, m);
+    std::vector<int> miss;
+    if (missing)
+        for (int i = 0; missing[i] > -1; i++) miss.push_back(missing[i]);
+    const std::vector<int> G = rs_generator(k, m);
+    if (G.empty() || rs_check_map(G, k, m, miss, fm) != 0)
+        return dev_fail(ECAMD_EINVAL, "too many missing fragments (%zu > m=%d)", miss.size(), m);
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ecamd_rs_check(int k, int m, const int* missing, const void* base, int64_t stripe_stride, int64_t frag_stride,
+                   int64_t blocksize, int nstripes, uint32_t* d_status, uint32_t* checked, void* stream)
+{
+    return rs_call(false, k, m, missing, base, stripe_stride, frag_stride, blocksize, nstripes, d_status, nullptr, checked,
+                   stream);
+}
+
+int ecamd_xor_check(int k, int m, int hd, const void* base, int64_t stripe_stride, int64_t frag_stride,
+                    int64_t blocksize, int nstripes, uint32_t* d_status, void* stream)
+{
+    return xor_call(false, k, m, hd, base, stripe_stride, frag_stride, blocksize, nstripes, d_status, nullptr, stream);
+}
+
+int ecamd_check_prebuild(int k, int m, const int* missing, const char* arch, const char* dir)
+{
+    FragmentMap fm;
+    const int rc = prebuild_plan("check", k, m, missing, arch, dir, fm);
+    if (rc) return rc;
+    const int R = static_cast<int>(fm.outputs.size()), K = static_cast<int>(fm.inputs.size());
+    int built = 0;
+    for (int row0 = 0; row0 < R; row0 += 8) {  // as run_check groups them
+        const int nrows = std::min(8, R - row0);
+        const int r = check_fused_prebuild(fm.coeff, K, row0, nrows, false, arch, dir);
+        if (r < 0) return dev_fail(ECAMD_EHIP, "check prebuild failed (%d) for a %dx%d map", r, nrows, K + nrows);
+        built += r;
+    }
+    return built;
+}
+
+int ecamd_rs_locate(int k, int m, const int* missing, const void* base, int64_t stripe_stride, int64_t frag_stride,
+                    int64_t blocksize, int nstripes, uint32_t* d_status, uint32_t* d_suspects, uint32_t* checked,
+                    void* stream)
+{
+    return rs_call(true, k, m, missing, base, stripe_stride, frag_stride, blocksize, nstripes, d_status, d_suspects, checked,
+                   stream);
+}
+
+int ecamd_xor_locate(int k, int m, int hd, const void* base, int64_t stripe_stride, int64_t frag_stride,
+                     int64_t blocksize, int nstripes, uint32_t* d_status, uint32_t* d_suspects, void* stream)
+{
+    return xor_call(true, k, m, hd, base, stripe_stride, frag_stride, blocksize, nstripes, d_status, d_suspects, stream);
+}
+
+int ecamd_rs_scrub(int k, int m, void* base, int64_t stripe_stride, int64_t frag_stride, int64_t blocksize,
+                   int nstripes, uint32_t* d_status, uint32_t* d_suspects, int* n_clean, int* n_repaired,
+                   int* n_unlocated, void* stream)
+{
+    if (m < 2) return dev_fail(ECAMD_EINVAL, "scrub needs m >= 2 to tell fragments apart (m=%d)", m);
+    int rc = ecamd_rs_locate(k, m, nullptr, base, stripe_stride, frag_stride, blocksize, nstripes, d_status, d_suspects,
+                             nullptr, stream);
+    if (rc) return rc;
+    int clean = 0, repaired = 0, unlocated = 0;
+    if (nstripes > 0) {
+        HIP_TRY(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
+        std::vector<uint32_t> status(static_cast<size_t>(nstripes)), suspects(static_cast<size_t>(nstripes));
+        HIP_TRY(hipMemcpy(status.data(), d_status, status.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(suspects.data(), d_suspects, suspects.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        std::vector<int> lists(static_cast<size_t>(nstripes) * 2, -1);  // {f, -1} or the empty list per stripe
+        for (int s = 0; s < nstripes; s++) {
+            const uint32_t sus = suspects[static_cast<size_t>(s)];
+            if (!status[static_cast<size_t>(s)])
+                clean++;
+            else if (sus && !(sus & (sus - 1))) {
+                lists[static_cast<size_t>(s) * 2] = __builtin_ctz(sus);
+                repaired++;
+            } else
+                unlocated++;
+        }
+        if (repaired &&
+            (rc = ecamd_rs_decode_multi(k, m, lists.data(), 2, 1, base, stripe_stride, frag_stride, blocksize, nstripes, stream)))
+            return rc;
+    }
+    if (n_clean) *n_clean = clean;
+    if (n_repaired) *n_repaired = repaired;
+    if (n_unlocated) *n_unlocated = unlocated;
+    return 0;
+}
+
+int ecamd_locate_prebuild(int k, int m, const int* missing, const char* arch, const char* dir)
+{
+    FragmentMap fm;
+    const int rc = prebuild_plan("locate", k, m, missing, arch, dir, fm);
+    if (rc) return rc;
+    const int R = static_cast<int>(fm.outputs.size()), K = static_cast<int>(fm.inputs.size());
+    if (R < 2) return 0;  // as run_check: the check's objects serve
+    const int r = check_fused_prebuild(fm.coeff, K, 0, R, true, arch, dir);
+    if (r == -6) return 0;  // every build needs scratch: the run time declines the fused form as well
+    if (r < 0) return dev_fail(ECAMD_EHIP, "locate prebuild failed (%d) for a %dx%d map", r, R, K + R);
+    return r;
+}
+
+}  // extern "C"

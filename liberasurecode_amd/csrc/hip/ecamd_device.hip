@@ -1476,6 +1476,62 @@ int64_t launch_bitslice(const ecamd_map* map, int row0, int nrows, const ApplyAr
     return *rc ? 0 : cover;
 }
 
+// Rows [row0, row0 + nrows) of the R x K matrix A as the syndrome matrix [A | I] over its K inputs
+// followed by those rows' own fragments: the one place the run time's request (check_fused) and the
+// shipped object's key (check_fused_prebuild) come from.
+std::vector<int> syndrome_rows(const std::vector<int>& A, int K, int row0, int nrows)
+{
+    const int W = K + nrows;
+    std::vector<int> syn(static_cast<size_t>(nrows) * W, 0);
+    for (int r = 0; r < nrows; r++) {
+        for (int j = 0; j < K; j++) syn[static_cast<size_t>(r) * W + j] = A[static_cast<size_t>(row0 + r) * K + j];
+        syn[static_cast<size_t>(r) * W + K + r] = 1;
+    }
+    return syn;
+}
+
+}  // namespace
+
+namespace ecamd {
+
+int64_t check_fused(int dev, const std::vector<int>& A, int K, int row0, int nrows, const uint8_t* base,
+                    int64_t stripe_stride, const int64_t* in_off, const int64_t* chk_off, const uint8_t* bits,
+                    uint32_t* d_status, uint32_t* d_suspects, const uint8_t* in_bits, int64_t blocksize, int nstripes,
+                    void* stream)
+{
+    if (nrows > kBsMaxR || K + nrows > kBsMaxK) return 0;
+    ecamd_map syn;
+    syn.device = dev;
+    syn.R = nrows;
+    syn.K = K + nrows;
+    syn.coeff = syndrome_rows(A, K, row0, nrows);
+    std::vector<int64_t> off(in_off, in_off + K);
+    off.insert(off.end(), chk_off + row0, chk_off + row0 + nrows);
+    std::vector<uint8_t> frag_bits(in_bits, in_bits + K);  // of the map's inputs: the K inputs, then the checked rows
+    frag_bits.insert(frag_bits.end(), bits + row0, bits + row0 + nrows);
+    ApplyArgs a{};
+    a.in_base = base;
+    a.in_stride = stripe_stride;
+    const BsCheck chk{d_status, bits + row0, d_suspects, frag_bits.data()};
+    int rc = 0;
+    const int64_t cover = launch_bitslice(&syn, 0, nrows, a, off.data(), nullptr, blocksize, nstripes,
+                                          static_cast<hipStream_t>(stream), &rc, nullptr, &chk);
+    return rc ? rc : cover;
+}
+
+int check_fused_prebuild(const std::vector<int>& A, int K, int row0, int nrows, bool locate, const char* arch,
+                         const char* dir)
+{
+    BsForm f;
+    if (nrows > kBsMaxR || K + nrows > kBsMaxK || !bs_form(nrows, K + nrows, false, false, f)) return 0;
+    return bitslice_prebuild(syndrome_rows(A, K, row0, nrows), nrows, K + nrows, f.depth, false, 0, f.wave, nullptr,
+                             f.prefetch, f.occ, arch, dir, true, locate);
+}
+
+}  // namespace ecamd
+
+namespace {
+
 template <bool PTRS>
 int launch_gf16(const ecamd_map* map, ApplyArgs base_args, const int64_t* in_off,
                 const int64_t* out_off, int64_t bs_all, int nstripes, hipStream_t st)
@@ -1845,6 +1901,19 @@ int rs_run(const RsEntry& e, void* base, int64_t stripe_stride, int64_t frag_str
 }  // namespace
 
 namespace ecamd {
+
+int check_map(int k, int m, const int* missing, CheckMap& out)
+{
+    std::shared_ptr<RsEntry> e;
+    const int rc = rs_entry(4, k, m, missing, 0, -1, e);
+    if (rc) return rc;
+    out.inputs = &e->inputs;
+    out.checked = &e->outputs;
+    out.map = e->map.get();
+    out.coeff = e->map ? &e->map->coeff : nullptr;
+    out.hold = e;
+    return 0;
+}
 
 namespace {
 
@@ -3841,638 +3910,8 @@ int ecamd_event_elapsed_ms(void* start, void* stop, float* ms)
     return 0;
 }
 
-}  // extern "C"
-
-// ---- stripe consistency check (ecamd_rs_check / ecamd_xor_check, DESIGN.md "Consistency check") ----
-//
-// Fused path (rs_vand, whole bitsliced tiles): the check form of the bitsliced kernel over the
-// syndrome map [A | I] reads the K inputs and the R checked fragments and writes only the status bits
-// of inconsistent stripes.  Generic path (everything else: tails, small fragments, shapes bs_form
-// declines, maps still compiling, knob bitslice 0, flat XOR): the existing kernels compute the
-// expected fragments into the stream context's scratch (slot kCheckScratchSlot, at most
-// kCheckScratchBytes, so long batches go stripe chunk by stripe chunk and long fragments byte range
-// by byte range) and check_compare_kernel compares them with the stored ones.  Both OR into the same
-// status words, which ecamd_*_check clears first.
-namespace {
-
-struct CheckCmpArgs {
-    const uint8_t* base;  // stored: row r of stripe s at base + s*stripe_stride + off[r]
-    const uint8_t* calc;  // computed: row r of stripe s at calc + (s*nrows + r)*pitch
-    uint32_t* status;     // of the launch's first stripe
-    int64_t stripe_stride;
-    int64_t pitch;
-    int64_t len;          // bytes compared per fragment
-    int64_t off[32];
-    uint8_t bit[32];
-    int nrows;
-};
-
-// grid (x, row, stripe): 16-byte pieces of exactly `len` bytes, the last piece masked to the
-// fragment's own bytes (read byte by byte, so nothing past `len` is ever touched); one atomicOr per
-// (wave, row) that differs, none for a wave that sees no difference.
-__global__ void __launch_bounds__(256) check_compare_kernel(CheckCmpArgs a)
-{
-    const int r = blockIdx.y;
-    const int64_t s = blockIdx.z;
-    const uint8_t* x = a.base + s * a.stripe_stride + a.off[r];
-    const uint8_t* y = a.calc + (s * a.nrows + r) * a.pitch;
-    const int64_t whole = a.len >> 4;
-    uint32_t d = 0;
-    for (int64_t p = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x; p < whole;
-         p += static_cast<int64_t>(gridDim.x) * 256) {
-        const uint4 u = *reinterpret_cast<const uint4*>(x + p * 16);
-        const uint4 v = *reinterpret_cast<const uint4*>(y + p * 16);
-        d |= (u.x ^ v.x) | (u.y ^ v.y) | (u.z ^ v.z) | (u.w ^ v.w);
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0)
-        for (int64_t i = whole << 4; i < a.len; i++) d |= static_cast<uint32_t>(x[i] ^ y[i]);
-    if (__ballot(d != 0u) != 0ull && (threadIdx.x & 63u) == 0u) atomicOr(a.status + s, 1u << a.bit[r]);
-}
-
-// Locate (ecamd_rs_locate / ecamd_xor_locate), generic path: the compare step also names the single
-// fragment that explains a stripe's disagreements.  The R x K map A (R checked rows over K inputs)
-// comes as rat[r*K + j] = A[r][j] / A[piv[j]][j], piv[j] the first row with A[r][j] != 0 and
-// colmask[j] the rows where it is non-zero (rs_vand: every row, piv 0; flat XOR: the parity bitmaps,
-// all ratios 1).  R * K <= 256 because K + R <= 32.
-constexpr int kLocMaxRK = 256;
-struct LocateCmpArgs {
-    const uint8_t* base;  // as CheckCmpArgs
-    const uint8_t* calc;
-    uint32_t* status;
-    uint32_t* suspects;  // of the launch's first stripe
-    int64_t stripe_stride;
-    int64_t pitch;
-    int64_t len;
-    int64_t off[32];
-    uint32_t colmask[32];
-    uint16_t rat[kLocMaxRK];
-    uint8_t piv[32];
-    uint8_t row_bit[32];  // fragment index of checked row r
-    uint8_t in_bit[32];   // fragment index of input j
-    int nrows, ncols;
-};
-
-// c times both 16-bit words of x in GF(2^16), polynomial 0x1100b: shift and xor, no table.
-__device__ __forceinline__ uint32_t gf16_mul2(uint32_t c, uint32_t x)
-{
-    uint32_t acc = 0;
-#pragma unroll
-    for (int b = 0; b < 16; b++) {
-        if ((c >> b) & 1u) acc ^= x;
-        const uint32_t hi = x & 0x80008000u;
-        x = ((x & 0x7fff7fffu) << 1) ^ ((hi >> 15) * 0x100bu);
-    }
-    return acc;
-}
-
-// Syndrome piece p (16 bytes) of one row: stored ^ computed; the last, partial piece byte by byte
-// and zero-padded, so nothing past `len` is ever read.
-__device__ __forceinline__ uint4 locate_piece(const uint8_t* x, const uint8_t* y, int64_t p, int64_t whole, int64_t len)
-{
-    if (p < whole) {
-        const uint4 u = *reinterpret_cast<const uint4*>(x + p * 16);
-        const uint4 v = *reinterpret_cast<const uint4*>(y + p * 16);
-        return uint4{u.x ^ v.x, u.y ^ v.y, u.z ^ v.z, u.w ^ v.w};
-    }
-    uint32_t w[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-    for (int i = 0; i < 16; i++) {
-        const int64_t q = (whole << 4) + i;
-        const uint32_t d = q < len ? static_cast<uint32_t>(x[q] ^ y[q]) : 0u;
-        w[i >> 2] |= d << (8 * (i & 3));
-    }
-    return uint4{w[0], w[1], w[2], w[3]};
-}
-
-// grid (x, stripe): one thread takes all R rows of a 16-byte piece.  Status bits as
-// check_compare_kernel.  For a dirty piece only: checked candidate c survives iff row c alone is
-// non-zero; input candidate j survives iff exactly the rows of colmask[j] are non-zero and
-// S_r == rat[r][j] * S_piv for each of them.  A dirty wave issues one atomicOr and one atomicAnd.
-__global__ void __launch_bounds__(256) locate_compare_kernel(LocateCmpArgs a)
-{
-    const int64_t s = blockIdx.y;
-    const uint8_t* xs = a.base + s * a.stripe_stride;
-    const uint8_t* ys = a.calc + s * a.nrows * a.pitch;
-    const int64_t whole = a.len >> 4, pieces = (a.len + 15) >> 4;
-    uint32_t st = 0u, keep = 0xffffffffu;
-    for (int64_t p = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x; p < pieces;
-         p += static_cast<int64_t>(gridDim.x) * 256) {
-        uint32_t nz = 0u;
-        for (int r = 0; r < a.nrows; r++) {
-            const uint4 d = locate_piece(xs + a.off[r], ys + r * a.pitch, p, whole, a.len);
-            if ((d.x | d.y | d.z | d.w) != 0u) nz |= 1u << r;
-        }
-        if (nz == 0u) continue;
-        for (int r = 0; r < a.nrows; r++) {
-            if ((nz >> r) & 1u) st |= 1u << a.row_bit[r];
-            if (nz != (1u << r)) keep &= ~(1u << a.row_bit[r]);
-        }
-        for (int j = 0; j < a.ncols; j++) {
-            bool ok = nz == a.colmask[j];
-            if (ok) {
-                const int pv = a.piv[j];
-                const uint4 s0 = locate_piece(xs + a.off[pv], ys + pv * a.pitch, p, whole, a.len);
-                for (int r = 0; r < a.nrows && ok; r++) {
-                    if (r == pv || !((nz >> r) & 1u)) continue;
-                    const uint32_t c = a.rat[r * a.ncols + j];
-                    const uint4 d = locate_piece(xs + a.off[r], ys + r * a.pitch, p, whole, a.len);
-                    ok = gf16_mul2(c, s0.x) == d.x && gf16_mul2(c, s0.y) == d.y && gf16_mul2(c, s0.z) == d.z &&
-                         gf16_mul2(c, s0.w) == d.w;
-                }
-            }
-            if (!ok) keep &= ~(1u << a.in_bit[j]);
-        }
-    }
-    for (int o = 32; o; o >>= 1) {
-        st |= __shfl_xor(st, o);
-        keep &= __shfl_xor(keep, o);
-    }
-    if ((threadIdx.x & 63u) == 0u && st != 0u) {
-        atomicOr(a.status + s, st);
-        atomicAnd(a.suspects + s, keep);
-    }
-}
-
-// suspects[s] = status[s] ? suspects[s] & participating : 0 (the last step of a locate call).
-__global__ void __launch_bounds__(256) locate_finalize_kernel(const uint32_t* status, uint32_t* suspects,
-                                                              uint32_t participating, int n)
-{
-    const int s = static_cast<int>(blockIdx.x) * 256 + static_cast<int>(threadIdx.x);
-    if (s < n) suspects[s] = status[s] ? suspects[s] & participating : 0u;
-}
-
-// Bytes [from, bs) of the nrows fragments at off[] (bit bits[r] each) of every stripe against what
-// apply(f0, len, s0, ns, calc, pitch) computes for bytes [f0, f0 + len) of stripes [s0, s0 + ns).
-// `from` a multiple of 16.  With `loc` (its map tables, fragment bits and suspects filled in) the compare
-// step is locate_compare_kernel, which writes the status bits too.
-template <class Apply>
-int check_generic(int dev, void* stream, const uint8_t* base, int64_t stripe_stride, const int64_t* off,
-                  const uint8_t* bits, int nrows, int64_t from, int64_t bs, int nstripes, uint32_t* d_status,
-                  Apply&& apply, const LocateCmpArgs* loc = nullptr)
-{
-    if (from >= bs || nrows <= 0 || nstripes <= 0) return 0;
-    if (nrows > 32) return fail(ECAMD_EINVAL, "check of %d fragments", nrows);
-    const int64_t cap = static_cast<int64_t>(kCheckScratchBytes);
-    const int64_t seg = std::max<int64_t>(65536, cap / nrows / 65536 * 65536);  // fragment bytes per pass
-    for (int64_t f0 = from; f0 < bs; f0 += seg) {
-        const int64_t len = std::min(seg, bs - f0);
-        const int64_t pitch = (len + 255) & ~int64_t(255);
-        const int per = static_cast<int>(std::min<int64_t>(std::clamp<int64_t>(cap / (pitch * nrows), 1, 65535), nstripes));
-        uint32_t* scratch = nullptr;
-        int rc = stream_scratch(dev, stream, kCheckScratchSlot, static_cast<size_t>(per) * nrows * pitch / 4, &scratch);
-        if (rc) return rc;
-        auto* calc = reinterpret_cast<uint8_t*>(scratch);
-        for (int s0 = 0; s0 < nstripes; s0 += per) {
-            const int ns = std::min(per, nstripes - s0);
-            if ((rc = apply(f0, len, s0, ns, calc, pitch))) return rc;
-            if (loc) {
-                LocateCmpArgs l = *loc;
-                l.base = base + s0 * stripe_stride + f0;
-                l.calc = calc;
-                l.status = d_status + s0;
-                l.suspects = loc->suspects + s0;
-                l.stripe_stride = stripe_stride;
-                l.pitch = pitch;
-                l.len = len;
-                l.nrows = nrows;
-                for (int r = 0; r < nrows; r++) {
-                    l.off[r] = off[r];
-                    l.row_bit[r] = bits[r];
-                }
-                const unsigned lx = static_cast<unsigned>(std::clamp<int64_t>((((len + 15) >> 4) + 1023) / 1024, 1, 1024));
-                hipLaunchKernelGGL(locate_compare_kernel, dim3(lx, static_cast<unsigned>(ns)), dim3(256), 0,
-                                   static_cast<hipStream_t>(stream), l);
-                HIP_TRY(hipGetLastError());
-                continue;
-            }
-            CheckCmpArgs c{};
-            c.base = base + s0 * stripe_stride + f0;
-            c.calc = calc;
-            c.status = d_status + s0;
-            c.stripe_stride = stripe_stride;
-            c.pitch = pitch;
-            c.len = len;
-            c.nrows = nrows;
-            for (int r = 0; r < nrows; r++) {
-                c.off[r] = off[r];
-                c.bit[r] = bits[r];
-            }
-            const unsigned gx = static_cast<unsigned>(std::clamp<int64_t>(((len >> 4) + 1023) / 1024, 1, 1024));
-            hipLaunchKernelGGL(check_compare_kernel, dim3(gx, static_cast<unsigned>(nrows), static_cast<unsigned>(ns)),
-                               dim3(256), 0, static_cast<hipStream_t>(stream), c);
-            HIP_TRY(hipGetLastError());
-        }
-    }
-    return 0;
-}
-
-int check_layout(const void* base, int64_t stripe_stride, int64_t frag_stride, int64_t blocksize, int nstripes,
-                 const uint32_t* d_status)
-{
-    if (!base || !d_status || nstripes < 0 || blocksize < 1 || frag_stride < blocksize)
-        return fail(ECAMD_EINVAL, "bad base / status / blocksize / strides");
-    if (!aligned16(base) || stripe_stride % 16 || frag_stride % 16)
-        return fail(ECAMD_EINVAL, "fragment addresses must be 16-byte aligned");
-    return 0;
-}
-
-// Rows [row0, row0 + nrows) of a check map as the syndrome matrix [A | I] over its K inputs followed
-// by those rows' own fragments.
-std::vector<int> syndrome_rows(const std::vector<int>& coeff, int K, int row0, int nrows)
-{
-    const int W = K + nrows;
-    std::vector<int> syn(static_cast<size_t>(nrows) * W, 0);
-    for (int r = 0; r < nrows; r++) {
-        for (int j = 0; j < K; j++) syn[static_cast<size_t>(r) * W + j] = coeff[static_cast<size_t>(row0 + r) * K + j];
-        syn[static_cast<size_t>(r) * W + K + r] = 1;
-    }
-    return syn;
-}
-
-}  // namespace
-
-extern "C" {
-
-int ecamd_rs_check(int k, int m, const int* missing, const void* base, int64_t stripe_stride, int64_t frag_stride,
-                   int64_t blocksize, int nstripes, uint32_t* d_status, uint32_t* checked, void* stream)
-{
-    int dev = 0;
-    int rc = ensure_device(&dev);
-    if (rc) return rc;
-    if (k <= 0 || m < 0 || k + m > 32) return fail(ECAMD_EINVAL, "check needs k + m <= 32 (k=%d m=%d)", k, m);
-    if ((rc = check_layout(base, stripe_stride, frag_stride, blocksize, nstripes, d_status))) return rc;
-    std::shared_ptr<RsEntry> e;
-    if ((rc = rs_entry(4, k, m, missing, 0, -1, e))) return rc;
-    const int K = static_cast<int>(e->inputs.size()), R = static_cast<int>(e->outputs.size());
-    uint32_t mask = 0;
-    for (int f : e->outputs) mask |= 1u << f;
-    if (checked) *checked = mask;
-    if (nstripes == 0) return 0;
-    const StreamUse use(dev, stream);  // the scratch of its stream context outlives this call
-    const auto st = static_cast<hipStream_t>(stream);
-    HIP_TRY(hipMemsetAsync(d_status, 0, static_cast<size_t>(nstripes) * sizeof(uint32_t), st));
-    if (R == 0) return 0;
-    const auto* b = static_cast<const uint8_t*>(base);
-    std::vector<int64_t> in_off, chk_off;
-    std::vector<uint8_t> bits;
-    for (int i : e->inputs) in_off.push_back(i * frag_stride);
-    for (int f : e->outputs) {
-        chk_off.push_back(f * frag_stride);
-        bits.push_back(static_cast<uint8_t>(f));
-    }
-    // whole tiles through the fused kernel, one launch per group of 8 rows; what every group covered
-    // is done, the rest of each fragment goes the generic way
-    int64_t cover = blocksize;
-    for (int row0 = 0; row0 < R; row0 += 8) {
-        const int nrows = std::min(8, R - row0);
-        int64_t done = 0;
-        if (K + nrows <= kBsMaxK) {
-            ecamd_map syn;
-            syn.device = dev;
-            syn.R = nrows;
-            syn.K = K + nrows;
-            syn.coeff = syndrome_rows(e->map->coeff, K, row0, nrows);
-            std::vector<int64_t> off(in_off);
-            off.insert(off.end(), chk_off.begin() + row0, chk_off.begin() + row0 + nrows);
-            ApplyArgs a{};
-            a.in_base = b;
-            a.in_stride = stripe_stride;
-            const BsCheck chk{d_status, bits.data() + row0};
-            int brc = 0;
-            done = launch_bitslice(&syn, 0, nrows, a, off.data(), nullptr, blocksize, nstripes, st, &brc, nullptr, &chk);
-            if (brc) return brc;
-        }
-        cover = std::min(cover, done);
-    }
-    return check_generic(dev, stream, b, stripe_stride, chk_off.data(), bits.data(), R, cover, blocksize, nstripes,
-                         d_status, [&](int64_t f0, int64_t len, int s0, int ns, uint8_t* calc, int64_t pitch) {
-                             ApplyArgs a{};
-                             a.in_base = b + s0 * stripe_stride;
-                             a.in_stride = stripe_stride;
-                             a.out_base = calc;
-                             a.out_stride = R * pitch;
-                             std::vector<int64_t> io(in_off), oo;
-                             for (auto& v : io) v += f0;
-                             for (int r = 0; r < R; r++) oo.push_back(r * pitch);
-                             return launch_gf16<false>(e->map.get(), a, io.data(), oo.data(), len, ns, st);
-                         });
-}
-
-int ecamd_xor_check(int k, int m, int hd, const void* base, int64_t stripe_stride, int64_t frag_stride,
-                    int64_t blocksize, int nstripes, uint32_t* d_status, void* stream)
-{
-    int dev = 0;
-    int rc = ensure_device(&dev);
-    if (rc) return rc;
-    unsigned pb[32], db[32];
-    if (k <= 0 || m <= 0 || k + m > 32 || ecamd_xor_code_tables(k, m, hd, pb, db) != 0)
-        return fail(ECAMD_EINVAL, "not a flat_xor_hd code: k=%d m=%d hd=%d", k, m, hd);
-    if ((rc = check_layout(base, stripe_stride, frag_stride, blocksize, nstripes, d_status))) return rc;
-    if (nstripes == 0) return 0;
-    const StreamUse use(dev, stream);
-    const auto st = static_cast<hipStream_t>(stream);
-    HIP_TRY(hipMemsetAsync(d_status, 0, static_cast<size_t>(nstripes) * sizeof(uint32_t), st));
-    const auto* b = static_cast<const uint8_t*>(base);
-    std::vector<int64_t> in_off, chk_off;
-    std::vector<uint8_t> bits;
-    std::vector<uint32_t> masks(pb, pb + m);
-    for (int j = 0; j < k; j++) in_off.push_back(j * frag_stride);
-    for (int p = 0; p < m; p++) {
-        chk_off.push_back((k + p) * frag_stride);
-        bits.push_back(static_cast<uint8_t>(k + p));
-    }
-    return check_generic(dev, stream, b, stripe_stride, chk_off.data(), bits.data(), m, 0, blocksize, nstripes, d_status,
-                         [&](int64_t f0, int64_t len, int s0, int ns, uint8_t* calc, int64_t pitch) {
-                             ApplyArgs a{};
-                             a.in_base = b + s0 * stripe_stride;
-                             a.in_stride = stripe_stride;
-                             a.out_base = calc;
-                             a.out_stride = m * pitch;
-                             std::vector<int64_t> io(in_off), oo;
-                             for (auto& v : io) v += f0;
-                             for (int r = 0; r < m; r++) oo.push_back(r * pitch);
-                             return launch_xor<false>(masks.data(), m, k, a, io.data(), oo.data(), len, ns, st);
-                         });
-}
-
+// what launch_bitslice counted for ecamd_check.hip
 long long ecamd_check_fused_launches(void) { return g_check_fused.load(std::memory_order_relaxed); }
-
-int ecamd_check_prebuild(int k, int m, const int* missing, const char* arch, const char* dir)
-{
-    if (!arch || !dir) return fail(ECAMD_EINVAL, "null arch / dir");
-    if (k <= 0 || m < 0 || k + m > 32) return fail(ECAMD_EINVAL, "check needs k + m <= 32 (k=%d m=%d)", k, m);
-    std::vector<int> miss;
-    if (missing)
-        for (int i = 0; missing[i] > -1; i++) miss.push_back(missing[i]);
-    const std::vector<int> G = rs_generator(k, m);
-    FragmentMap fm;
-    if (G.empty() || rs_check_map(G, k, m, miss, fm) != 0)
-        return fail(ECAMD_EINVAL, "too many missing fragments (%zu > m=%d)", miss.size(), m);
-    const int R = static_cast<int>(fm.outputs.size()), K = static_cast<int>(fm.inputs.size());
-    int built = 0;
-    for (int row0 = 0; row0 < R; row0 += 8) {
-        const int nrows = std::min(8, R - row0);
-        BsForm f;
-        if (!bs_form(nrows, K + nrows, false, false, f)) continue;
-        const int r = ecamd::bitslice_prebuild(syndrome_rows(fm.coeff, K, row0, nrows), nrows, K + nrows, f.depth, false, 0,
-                                               f.wave, nullptr, f.prefetch, f.occ, arch, dir, true);
-        if (r < 0) return fail(ECAMD_EHIP, "check prebuild failed (%d) for a %dx%d map", r, nrows, K + nrows);
-        built += r;
-    }
-    return built;
-}
-
-}  // extern "C"
-
-// ---- locate and scrub (ecamd_rs_locate / ecamd_xor_locate / ecamd_rs_scrub, DESIGN.md "Locate and scrub") ----
-//
-// d_status as the check writes it; d_suspects[s] the fragments that ALONE explain every disagreement
-// of stripe s.  The call sets the suspects to all-ones, every kernel ANDs the candidates it rules
-// out away (fused: the locate form of the bitsliced kernel over whole tiles; generic:
-// locate_compare_kernel over the rest), and locate_finalize_kernel masks the result with the
-// participating fragments and clears it on clean stripes -- all on the caller's stream, in order.
-namespace {
-
-int locate_args(const void* base, int64_t stripe_stride, int64_t frag_stride, int64_t blocksize, int nstripes,
-                const uint32_t* d_status, const uint32_t* d_suspects)
-{
-    const int rc = check_layout(base, stripe_stride, frag_stride, blocksize, nstripes, d_status);
-    if (rc) return rc;
-    if (!d_suspects) return fail(ECAMD_EINVAL, "null suspects");
-    // an odd size ends in half a word, whose product is cut to 8 bits: proportionality cannot be tested
-    if (blocksize & 1) return fail(ECAMD_EINVAL, "locate needs an even blocksize (%lld)", static_cast<long long>(blocksize));
-    return 0;
-}
-
-int locate_finalize(const uint32_t* d_status, uint32_t* d_suspects, uint32_t participating, int nstripes, hipStream_t st)
-{
-    hipLaunchKernelGGL(locate_finalize_kernel, dim3(static_cast<unsigned>((nstripes + 255) / 256)), dim3(256), 0, st,
-                       d_status, d_suspects, participating, nstripes);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-// The map tables of LocateCmpArgs for the R x K matrix A (row-major; entries 0..0xffff).
-void locate_tables(const std::vector<int>& A, int R, int K, LocateCmpArgs& l)
-{
-    const GF16& gf = GF16::get();
-    l.nrows = R;
-    l.ncols = K;
-    for (int j = 0; j < K; j++) {
-        int pv = -1;
-        uint32_t mask = 0;
-        for (int r = 0; r < R; r++)
-            if (A[static_cast<size_t>(r) * K + j]) {
-                if (pv < 0) pv = r;
-                mask |= 1u << r;
-            }
-        l.piv[j] = static_cast<uint8_t>(std::max(pv, 0));
-        l.colmask[j] = mask;
-        for (int r = 0; r < R; r++)
-            l.rat[r * K + j] = pv < 0 ? 0 : static_cast<uint16_t>(gf.mul(A[static_cast<size_t>(r) * K + j],
-                                                                         gf.inv(A[static_cast<size_t>(pv) * K + j])));
-    }
-}
-
-}  // namespace
-
-extern "C" {
-
-int ecamd_rs_locate(int k, int m, const int* missing, const void* base, int64_t stripe_stride, int64_t frag_stride,
-                    int64_t blocksize, int nstripes, uint32_t* d_status, uint32_t* d_suspects, uint32_t* checked,
-                    void* stream)
-{
-    int dev = 0;
-    int rc = ensure_device(&dev);
-    if (rc) return rc;
-    if (k <= 0 || m < 0 || k + m > 32) return fail(ECAMD_EINVAL, "locate needs k + m <= 32 (k=%d m=%d)", k, m);
-    if ((rc = locate_args(base, stripe_stride, frag_stride, blocksize, nstripes, d_status, d_suspects))) return rc;
-    std::shared_ptr<RsEntry> e;
-    if ((rc = rs_entry(4, k, m, missing, 0, -1, e))) return rc;
-    const int K = static_cast<int>(e->inputs.size()), R = static_cast<int>(e->outputs.size());
-    uint32_t mask = 0, participating = 0;
-    for (int f : e->outputs) mask |= 1u << f;
-    for (int f : e->inputs) participating |= 1u << f;
-    participating |= mask;
-    if (nstripes == 0) {
-        if (checked) *checked = mask;
-        return 0;
-    }
-    const StreamUse use(dev, stream);
-    const auto st = static_cast<hipStream_t>(stream);
-    HIP_TRY(hipMemsetAsync(d_suspects, 0xff, static_cast<size_t>(nstripes) * sizeof(uint32_t), st));
-    if (R < 2) {  // nothing to tell apart: the check, then every participating fragment of a dirty stripe
-        if ((rc = ecamd_rs_check(k, m, missing, base, stripe_stride, frag_stride, blocksize, nstripes, d_status, checked,
-                                 stream)))
-            return rc;
-        return locate_finalize(d_status, d_suspects, participating, nstripes, st);
-    }
-    if (checked) *checked = mask;
-    HIP_TRY(hipMemsetAsync(d_status, 0, static_cast<size_t>(nstripes) * sizeof(uint32_t), st));
-    const auto* b = static_cast<const uint8_t*>(base);
-    std::vector<int64_t> in_off, chk_off;
-    std::vector<uint8_t> bits, frag_bits;
-    for (int i : e->inputs) {
-        in_off.push_back(i * frag_stride);
-        frag_bits.push_back(static_cast<uint8_t>(i));
-    }
-    for (int f : e->outputs) {
-        chk_off.push_back(f * frag_stride);
-        bits.push_back(static_cast<uint8_t>(f));
-        frag_bits.push_back(static_cast<uint8_t>(f));
-    }
-    // whole tiles through the fused kernel: one launch over all R rows (the second stage needs every
-    // row's syndrome in one wave, so more than 8 rows take the generic path alone)
-    int64_t cover = 0;
-    if (R <= kBsMaxR && K + R <= kBsMaxK) {
-        ecamd_map syn;
-        syn.device = dev;
-        syn.R = R;
-        syn.K = K + R;
-        syn.coeff = syndrome_rows(e->map->coeff, K, 0, R);
-        std::vector<int64_t> off(in_off);
-        off.insert(off.end(), chk_off.begin(), chk_off.end());
-        ApplyArgs a{};
-        a.in_base = b;
-        a.in_stride = stripe_stride;
-        const BsCheck chk{d_status, bits.data(), d_suspects, frag_bits.data()};
-        int brc = 0;
-        cover = launch_bitslice(&syn, 0, R, a, off.data(), nullptr, blocksize, nstripes, st, &brc, nullptr, &chk);
-        if (brc) return brc;
-    }
-    LocateCmpArgs loc{};
-    loc.suspects = d_suspects;
-    locate_tables(e->map->coeff, R, K, loc);
-    for (int j = 0; j < K; j++) loc.in_bit[j] = frag_bits[static_cast<size_t>(j)];
-    rc = check_generic(dev, stream, b, stripe_stride, chk_off.data(), bits.data(), R, cover, blocksize, nstripes, d_status,
-                       [&](int64_t f0, int64_t len, int s0, int ns, uint8_t* calc, int64_t pitch) {
-                           ApplyArgs a{};
-                           a.in_base = b + s0 * stripe_stride;
-                           a.in_stride = stripe_stride;
-                           a.out_base = calc;
-                           a.out_stride = R * pitch;
-                           std::vector<int64_t> io(in_off), oo;
-                           for (auto& v : io) v += f0;
-                           for (int r = 0; r < R; r++) oo.push_back(r * pitch);
-                           return launch_gf16<false>(e->map.get(), a, io.data(), oo.data(), len, ns, st);
-                       },
-                       &loc);
-    if (rc) return rc;
-    return locate_finalize(d_status, d_suspects, participating, nstripes, st);
-}
-
-int ecamd_xor_locate(int k, int m, int hd, const void* base, int64_t stripe_stride, int64_t frag_stride,
-                     int64_t blocksize, int nstripes, uint32_t* d_status, uint32_t* d_suspects, void* stream)
-{
-    int dev = 0;
-    int rc = ensure_device(&dev);
-    if (rc) return rc;
-    unsigned pb[32], db[32];
-    if (k <= 0 || m <= 0 || k + m > 32 || ecamd_xor_code_tables(k, m, hd, pb, db) != 0)
-        return fail(ECAMD_EINVAL, "not a flat_xor_hd code: k=%d m=%d hd=%d", k, m, hd);
-    if ((rc = locate_args(base, stripe_stride, frag_stride, blocksize, nstripes, d_status, d_suspects))) return rc;
-    if (nstripes == 0) return 0;
-    const StreamUse use(dev, stream);
-    const auto st = static_cast<hipStream_t>(stream);
-    HIP_TRY(hipMemsetAsync(d_suspects, 0xff, static_cast<size_t>(nstripes) * sizeof(uint32_t), st));
-    const uint32_t participating = k + m >= 32 ? 0xffffffffu : (1u << (k + m)) - 1u;
-    if (m < 2) {
-        if ((rc = ecamd_xor_check(k, m, hd, base, stripe_stride, frag_stride, blocksize, nstripes, d_status, stream)))
-            return rc;
-        return locate_finalize(d_status, d_suspects, participating, nstripes, st);
-    }
-    HIP_TRY(hipMemsetAsync(d_status, 0, static_cast<size_t>(nstripes) * sizeof(uint32_t), st));
-    const auto* b = static_cast<const uint8_t*>(base);
-    std::vector<int64_t> in_off, chk_off;
-    std::vector<uint8_t> bits;
-    std::vector<uint32_t> masks(pb, pb + m);
-    std::vector<int> A(static_cast<size_t>(m) * k);  // the 0 / 1 parity bitmaps as a map over GF(2^16)
-    for (int p = 0; p < m; p++)
-        for (int j = 0; j < k; j++) A[static_cast<size_t>(p) * k + j] = (pb[p] >> j) & 1u;
-    LocateCmpArgs loc{};
-    loc.suspects = d_suspects;
-    locate_tables(A, m, k, loc);
-    for (int j = 0; j < k; j++) {
-        in_off.push_back(j * frag_stride);
-        loc.in_bit[j] = static_cast<uint8_t>(j);
-    }
-    for (int p = 0; p < m; p++) {
-        chk_off.push_back((k + p) * frag_stride);
-        bits.push_back(static_cast<uint8_t>(k + p));
-    }
-    rc = check_generic(dev, stream, b, stripe_stride, chk_off.data(), bits.data(), m, 0, blocksize, nstripes, d_status,
-                       [&](int64_t f0, int64_t len, int s0, int ns, uint8_t* calc, int64_t pitch) {
-                           ApplyArgs a{};
-                           a.in_base = b + s0 * stripe_stride;
-                           a.in_stride = stripe_stride;
-                           a.out_base = calc;
-                           a.out_stride = m * pitch;
-                           std::vector<int64_t> io(in_off), oo;
-                           for (auto& v : io) v += f0;
-                           for (int r = 0; r < m; r++) oo.push_back(r * pitch);
-                           return launch_xor<false>(masks.data(), m, k, a, io.data(), oo.data(), len, ns, st);
-                       },
-                       &loc);
-    if (rc) return rc;
-    return locate_finalize(d_status, d_suspects, participating, nstripes, st);
-}
-
-int ecamd_rs_scrub(int k, int m, void* base, int64_t stripe_stride, int64_t frag_stride, int64_t blocksize,
-                   int nstripes, uint32_t* d_status, uint32_t* d_suspects, int* n_clean, int* n_repaired,
-                   int* n_unlocated, void* stream)
-{
-    if (m < 2) return fail(ECAMD_EINVAL, "scrub needs m >= 2 to tell fragments apart (m=%d)", m);
-    int rc = ecamd_rs_locate(k, m, nullptr, base, stripe_stride, frag_stride, blocksize, nstripes, d_status, d_suspects,
-                             nullptr, stream);
-    if (rc) return rc;
-    int clean = 0, repaired = 0, unlocated = 0;
-    if (nstripes > 0) {
-        HIP_TRY(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
-        std::vector<uint32_t> status(static_cast<size_t>(nstripes)), suspects(static_cast<size_t>(nstripes));
-        HIP_TRY(hipMemcpy(status.data(), d_status, status.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(suspects.data(), d_suspects, suspects.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        std::vector<int> lists(static_cast<size_t>(nstripes) * 2, -1);  // {f, -1} or the empty list per stripe
-        for (int s = 0; s < nstripes; s++) {
-            const uint32_t sus = suspects[static_cast<size_t>(s)];
-            if (!status[static_cast<size_t>(s)])
-                clean++;
-            else if (sus && !(sus & (sus - 1))) {
-                lists[static_cast<size_t>(s) * 2] = __builtin_ctz(sus);
-                repaired++;
-            } else
-                unlocated++;
-        }
-        if (repaired &&
-            (rc = ecamd_rs_decode_multi(k, m, lists.data(), 2, 1, base, stripe_stride, frag_stride, blocksize, nstripes, stream)))
-            return rc;
-    }
-    if (n_clean) *n_clean = clean;
-    if (n_repaired) *n_repaired = repaired;
-    if (n_unlocated) *n_unlocated = unlocated;
-    return 0;
-}
-
 long long ecamd_locate_fused_launches(void) { return g_locate_fused.load(std::memory_order_relaxed); }
-
-int ecamd_locate_prebuild(int k, int m, const int* missing, const char* arch, const char* dir)
-{
-    if (!arch || !dir) return fail(ECAMD_EINVAL, "null arch / dir");
-    if (k <= 0 || m < 0 || k + m > 32) return fail(ECAMD_EINVAL, "locate needs k + m <= 32 (k=%d m=%d)", k, m);
-    std::vector<int> miss;
-    if (missing)
-        for (int i = 0; missing[i] > -1; i++) miss.push_back(missing[i]);
-    const std::vector<int> G = rs_generator(k, m);
-    FragmentMap fm;
-    if (G.empty() || rs_check_map(G, k, m, miss, fm) != 0)
-        return fail(ECAMD_EINVAL, "too many missing fragments (%zu > m=%d)", miss.size(), m);
-    const int R = static_cast<int>(fm.outputs.size()), K = static_cast<int>(fm.inputs.size());
-    BsForm f;
-    if (R < 2 || R > kBsMaxR || K + R > kBsMaxK || !bs_form(R, K + R, false, false, f)) return 0;
-    const int r = ecamd::bitslice_prebuild(syndrome_rows(fm.coeff, K, 0, R), R, K + R, f.depth, false, 0, f.wave, nullptr,
-                                           f.prefetch, f.occ, arch, dir, true, true);
-    if (r == -6) return 0;  // every build needs scratch: the run time declines the fused form as well
-    if (r < 0) return fail(ECAMD_EHIP, "locate prebuild failed (%d) for a %dx%d map", r, R, K + R);
-    return r;
-}
 
 }  // extern "C"

@@ -4,7 +4,10 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <memory>
 #include <mutex>
+
+struct ecamd_map;
 
 namespace ecamd {
 
@@ -55,8 +58,8 @@ int side_join(int dev, void* stream);
 // on one stream are ordered, so reuse is safe (slot 1 holds values that must outlive a CRC pass on
 // the same stream, whose partials use slot 0).
 // Slot 4: the small-launch fused CRC's counter and partials (ecamd_map_apply_strided_crc).  A slot is
-// zeroed when it is (re)allocated.  Slot 5: the fragments ecamd_rs_check / ecamd_xor_check compute to
-// compare the stored ones against (generic path; at most kCheckScratchBytes).
+// zeroed when it is (re)allocated.  Slot 5: the fragments the checks and locates of ecamd_check.hip
+// compute to compare the stored ones against (generic stage; at most kCheckScratchBytes).
 constexpr int kStreamScratchSlots = 6;
 constexpr int kSmallCrcScratchSlot = 4;
 constexpr int kCheckScratchSlot = 5;
@@ -76,6 +79,34 @@ struct StreamUse {
 };
 void stream_forget(void* stream);
 int stream_contexts();
+
+// What ecamd_check.hip (check, locate, scrub) takes from ecamd_device.hip.
+// The cached check map of the rs_vand code (k, m) with `missing` (-1 terminated, may be null) lost:
+// the first k available fragments are the inputs, every other available one is checked.  `hold` keeps
+// the entry alive past its eviction from the map cache.  ECAMD_EINVAL for too many missing fragments.
+struct CheckMap {
+    const std::vector<int>* inputs = nullptr;   // fragment indices of the K inputs
+    const std::vector<int>* checked = nullptr;  // fragment indices of the R checked fragments
+    const std::vector<int>* coeff = nullptr;    // R x K, row-major (null when R == 0)
+    const ecamd_map* map = nullptr;             // the same map for the apply calls (null when R == 0)
+    std::shared_ptr<const void> hold;
+};
+int check_map(int k, int m, const int* missing, CheckMap& out);
+// Fused stage of a check or, with d_suspects, of a locate: rows [row0, row0 + nrows) of the R x K
+// matrix A as the syndrome map [A | I] through the check / locate form of the bitsliced kernel, over
+// whole tiles of every stripe.  Input j of stripe s at base + s*stripe_stride + in_off[j], fragment
+// index in_bits[j]; checked row r at chk_off[r], fragment index bits[r] (both arrays of all R rows).
+// Returns the bytes of each fragment covered -- 0 when the shape, the knobs or a kernel still
+// compiling decline, nothing launched -- or an error (< 0).
+int64_t check_fused(int dev, const std::vector<int>& A, int K, int row0, int nrows, const uint8_t* base,
+                    int64_t stripe_stride, const int64_t* in_off, const int64_t* chk_off, const uint8_t* bits,
+                    uint32_t* d_status, uint32_t* d_suspects, const uint8_t* in_bits, int64_t blocksize, int nstripes,
+                    void* stream);
+// Build time (no GPU): the code object check_fused will ask for over the same rows, into `dir`
+// (bitslice_prebuild's result: 1 present, 0 no fused form under the current knobs, < 0 failed; -6
+// from the locate form: every build needs scratch, so the run time declines it too).
+int check_fused_prebuild(const std::vector<int>& A, int K, int row0, int nrows, bool locate, const char* arch,
+                         const char* dir);
 
 int rs_encode_copy(int k, int m, const void* obj, int64_t obj_stride, void* payload0,
                    int64_t stripe_stride, int64_t frag_stride, int64_t bs, int nstripes,

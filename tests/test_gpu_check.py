@@ -146,6 +146,34 @@ def test_one_bit_flips_match_the_oracle(D, dev, k, m):
         assert (got == want).all(), (f, p, [hex(x) for x in got], [hex(x) for x in want])
 
 
+# rs_vand (8, 12): R = 12 checked fragments in two row groups.  At this size group 0 (8 rows, 16 KiB
+# tiles) covers 16384 bytes and group 1 (4 rows, one-wave 4 KiB tiles) 20480; the generic stage redoes
+# everything past the SMALLER cover for all rows, so bytes [16384, 20480) of group 1's rows are seen
+# by both stages.  (fragment, byte) of the flip in stripe 1: none, an input, a row of each group, one
+# where the stages overlap, one in the 48-byte tail.
+WIDE = (8, 12, 16384 + 4096 + TAIL)
+WIDE_FLIPS = [None, (3, 5000), (9, 100), (17, 16384 + 1000), (12, 16384 + 4096 + 20)]
+
+
+def test_twelve_checked_fragments_in_two_row_groups(D, dev):
+    """Judged by the statuses alone: a group whose network is declined goes the generic way, which
+    must be just as right."""
+    k, m, bs = WIDE
+    full = stripes(k, m, bs)
+    n0 = dev.ecamd_check_fused_launches()
+    for flip in WIDE_FLIPS:
+        held = np.array(full)
+        if flip:
+            held[1, flip[0], flip[1]] ^= 0x04
+        want, mask = oracle_status(k, m, held, [])
+        assert mask == 0xFFF << k and not want[0] and not want[2]
+        assert want[1] == (0 if not flip else mask if flip[0] < k else 1 << flip[0])
+        got, checked = run_check(D, k, m, held)
+        assert checked == mask
+        assert (got == want).all(), (flip, [hex(x) for x in got], [hex(x) for x in want])
+    print("ecamd_check_fused_launches rose by", dev.ecamd_check_fused_launches() - n0, "over", len(WIDE_FLIPS), "checks")
+
+
 @pytest.mark.parametrize("missing", [[2, 7], [0]])
 def test_missing_fragments(D, dev, missing):
     k, m = 10, 4

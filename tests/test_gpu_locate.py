@@ -136,6 +136,25 @@ def test_two_flips_in_one_fragment_and_in_two(D, dev, k, m):
         assert (st == want_st).all() and st[1] and not su.any(), ((f1, p1), (f2, p2), hexes(st), hexes(su))
 
 
+def test_twelve_checked_fragments_take_the_generic_path_alone(D, dev):
+    """rs_vand (8, 12), R = 12: the fused locate needs every row's syndrome in one wave, so more than
+    8 rows go through the compare kernel alone (the cases of test_gpu_check.WIDE_FLIPS)."""
+    k, m, bs = TC.WIDE
+    full = TC.stripes(k, m, bs)
+    n0 = dev.ecamd_locate_fused_launches()
+    for flip in TC.WIDE_FLIPS:
+        held = np.array(full)
+        if flip:
+            held[1, flip[0], flip[1]] ^= 0x04
+        want_st, want_su = oracle_locate(k, m, held, [])
+        assert want_su[1] == (1 << flip[0] if flip else 0) and not want_su[0] and not want_su[2]
+        st, su, checked = run_locate(D, k, m, held)
+        assert checked == 0xFFF << k
+        assert (st == want_st).all(), (flip, hexes(st), hexes(want_st))
+        assert (su == want_su).all(), (flip, hexes(su), hexes(want_su))
+    assert dev.ecamd_locate_fused_launches() == n0
+
+
 @pytest.mark.parametrize("missing", [[0], [2, 7]])
 def test_missing_fragments(D, dev, missing):
     k, m = 10, 4

@@ -1,6 +1,6 @@
 """GPU: the generic path's chunk loops, and scrub on (20,8) and (4,2).
 
-check_generic (csrc/hip/ecamd_device.hip) walks a batch in stripe chunks over the shared scratch of
+check_generic (csrc/hip/ecamd_check.hip) walks a batch in stripe chunks over the shared scratch of
 kCheckScratchBytes and a long fragment in byte ranges, with a clamp of its own at 65535 stripes for the
 grid's y / z limit.  The tests here are sized so that each loop iterates twice: data are made on the
 device (fill_splitmix + encode), damaged with a few small uploads, and the expected words of the damaged
