@@ -55,6 +55,19 @@ int ecamd_bitslice_wait(void);
 int ecamd_bitslice_entries(void);
 /* Bitsliced kernel launches this process has enqueued (tests pin which kernel ran). */
 long long ecamd_bitslice_launches(void);
+/* ---- Development hooks: for the project's tests and tools, not part of the product API ---- */
+/* Test scaffolding (tests/test_bitslice_launch_forms.py): the cache name (no directory, no ".co") of
+ * the code object of a compile request text for target `arch`, as the shipped directory and the
+ * per-user cache hold it: its length, < 0 on error. */
+int ecamd_bitslice_object_name(const char *request, const char *arch, char *buf, int size);
+/* Measurement hook (tools/launch_timeline.py; DESIGN.md §4 "Per-launch cost" says why it is a call and
+ * not an environment variable): while `records` > 0, launches of the plain one-wave bitsliced kernel
+ * -- from every thread of the process, so call it from a tool that launches from one -- run its
+ * timeline form, which writes tile t's 32-byte record {start, end (64-bit ticks of the 100 MHz wall
+ * clock), tile, XCC id, hardware id, 0} to buf + 32 t for t < records.  `buf` is device memory the
+ * caller owns and keeps until those launches have finished; records 0 turns it off.  Results are
+ * unchanged. */
+int ecamd_bitslice_timeline(void *buf, unsigned records);
 
 /* Which kernel an rs_vand operation's passes run on this process's current device, for fragments
  * of `blocksize` bytes: encode (missing NULL), decode of the -1 terminated `missing` (dest < 0;

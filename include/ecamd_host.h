@@ -131,6 +131,16 @@ int ecamd_bitslice_eval(const int *coeff, int R, int K, int cap, const uint16_t 
                         int *ops);
 int64_t ecamd_bitslice_source(const int *coeff, int R, int K, int cap, int depth, char *buf,
                               int64_t size);
+/* Test scaffolding (tests/test_bitslice_launch_forms.py), not part of the product API: what the
+ * generator makes of a request, without a GPU or a compile.
+ * Compile requests as libecamd writes them and ecamd_jitc reads them (bitslice_request): the text of
+ * the plain one-wave form's request for an R x K matrix with the given option bits (kBsOpt*, 0:
+ * none), the option bits a request text parses to (-1: not a request), and the source ecamd_jitc
+ * compiles for a request text (-1: not a request).  Lengths and buffers as ecamd_bitslice_source. */
+int64_t ecamd_bitslice_wave_request(const int *coeff, int R, int K, int cap, int opts, char *buf,
+                                    int64_t size);
+int ecamd_bitslice_request_opts(const char *request);
+int64_t ecamd_bitslice_request_source(const char *request, char *buf, int64_t size);
 
 #ifdef __cplusplus
 }

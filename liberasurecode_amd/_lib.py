@@ -60,6 +60,10 @@ def host():
                [IP, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, IP])
         _proto(h, "ecamd_bitslice_source", C.c_int64,
                [IP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_int64])
+        _proto(h, "ecamd_bitslice_wave_request", C.c_int64,
+               [IP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_int64])
+        _proto(h, "ecamd_bitslice_request_opts", C.c_int, [C.c_char_p])
+        _proto(h, "ecamd_bitslice_request_source", C.c_int64, [C.c_char_p, C.c_char_p, C.c_int64])
         _proto(h, "ecamd_split_tables", C.c_int,
                [IP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p])
         _host = h
@@ -131,6 +135,8 @@ def dev():
         _proto(d, "ecamd_bitslice_wait", C.c_int, [])
         _proto(d, "ecamd_bitslice_entries", C.c_int, [])
         _proto(d, "ecamd_bitslice_launches", C.c_longlong, [])
+        _proto(d, "ecamd_bitslice_object_name", C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int])
+        _proto(d, "ecamd_bitslice_timeline", C.c_int, [VP, C.c_uint])
         _proto(d, "ecamd_rs_kernel_form", C.c_int, [C.c_int, C.c_int, VP, C.c_int, C.c_int, C.c_int64])
         _proto(d, "ecamd_bitslice_prebuild", C.c_int,
                [C.c_int, C.c_int, VP, C.c_int, C.c_int, C.c_char_p, C.c_char_p])

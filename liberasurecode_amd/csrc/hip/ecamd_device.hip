@@ -408,6 +408,16 @@ struct Tuning {
                                   //   profiles/r04_frame_wave_pf_ab2.log)
     Knob bs_tiles_per_slot{16};   // ecamd_bs_kernel: the same for bitsliced passes (0: one launch;
                                   //   16: C5 x 128 stripes +3%, tools/bs_slot_sweep.py)
+    Knob bs_store_through{-1};    // ecamd_bs_kernel, plain one-wave maps: outputs stored write-through (sc0 sc1 nt: the
+                                  //   lines go straight to memory, not through an L2 allocation evicted later); 1
+                                  //   always, 0 never (the kernel as it was), < 0 by shape: maps of 2 to 4 outputs
+                                  //   (bs_form).  Measured on 4-output maps -- C3 step (encode + decode {0,1,2,3})
+                                  //   1.5-1.8% faster at 256 and 64 stripes, mixed decode +0.8% -- and on one 2-output
+                                  //   decode (+0.7%); 3-output maps sit between and were not measured, 5-8-output
+                                  //   maps in one-wave tiles (bs_wave 2) neither and keep nt; 1-output maps ran
+                                  //   0.6-1.3% SLOWER and keep nt.  The per-shape figures are medians of five
+                                  //   interleaved rounds each (tools/launch_timeline.py ab / other,
+                                  //   profiles/r07_launch_knob_ab.json; DESIGN.md §4 "Per-launch cost")
     Knob xor_tiles_per_slot{32};  // xor_stream_kernel: the same for flat XOR passes (0: one launch;
                                   //   32 measured best with the 12-wave geometry, (3,3,3) C1 +2%,
                                   //   tools/xor_geom_sweep.py; 64 before)
@@ -518,10 +528,10 @@ namespace ecamd {
 hipFunction_t bitslice_function(int dev, const std::vector<int>& coeff, int R, int K, int depth, bool wait,
                                 std::shared_ptr<void>& hold, bool copy = false, int crc = 0, bool wave = false,
                                 const std::vector<int>* in_shift = nullptr, int prefetch = 0, int* status = nullptr,
-                                const BsOcc* occ = nullptr, bool check = false, bool locate = false);
+                                const BsOcc* occ = nullptr, bool check = false, bool locate = false, int opts = 0);
 int bitslice_prebuild(const std::vector<int>& coeff, int R, int K, int depth, bool copy, int crc, bool wave,
                       const std::vector<int>* in_shift, int prefetch, const BsOcc& occ, const std::string& arch,
-                      const std::string& dir, bool check = false, bool locate = false);
+                      const std::string& dir, bool check = false, bool locate = false, int opts = 0);
 int bitslice_launch(hipFunction_t fn, const BsArgs& args, int grid, hipStream_t st,
                     const std::shared_ptr<void>& hold, int threads = 256, unsigned lds = 0);
 }  // namespace ecamd
@@ -1309,7 +1319,14 @@ struct BsForm {
     int depth = 0;      // LDS ring depth (0: register loads)
     int prefetch = 0;   // BitsliceStyle::prefetch (copy-through forms)
     BsOcc occ;          // one-wave forms: occupancy (knobs bs_wave_wmin / bs_wave_wmax / bs_wave_barrier)
+    int opts = 0;       // plain one-wave register form: kBsOpt* bits (knob bs_store_through, ecamd_bitslice_timeline)
 };
+// ecamd_bitslice_timeline's buffer (a development hook, measurement only): while set, the plain one-wave
+// form runs its timeline form -- in every thread of the process, so the hook is for a tool that launches
+// from one thread.  The two words are not set together: bs_form may still see the old count, and the
+// launcher reads both again and hands the kernel a null buffer with a count of 0 whenever they disagree.
+std::atomic<uint32_t*> g_timeline{nullptr};
+std::atomic<uint32_t> g_timeline_records{0};
 bool bs_form(int nrows, int K, bool copy, bool unaligned, BsForm& f)
 {
     if (!g_tune.bitslice || nrows <= 0 || nrows > kBsMaxR || K <= 0 || K > kBsMaxK) return false;
@@ -1329,6 +1346,12 @@ bool bs_form(int nrows, int K, bool copy, bool unaligned, BsForm& f)
                  : !copy ? (f.wave ? static_cast<int>(g_tune.bs_plain_prefetch) : 0)
                          : f.wave ? static_cast<int>(g_tune.bs_prefetch) : static_cast<int>(g_tune.bs_late_copy);
     f.occ = wave_occ(nrows, copy);
+    f.opts = 0;
+    if (f.wave && !copy && f.depth == 0) {
+        const int through = static_cast<int>(g_tune.bs_store_through);
+        f.opts = ((through < 0 ? nrows >= 2 && nrows <= 4 : through > 0) ? kBsOptStoreThrough : 0) |
+                 (g_timeline_records.load(std::memory_order_relaxed) ? kBsOptTimeline : 0);
+    }
     if (!f.wave) {  // multi-wave form: its workgroup size (plain register form only; bs_tile_threads)
         f.occ = BsOcc{};
         const int t = static_cast<int>(g_tune.bs_tile_threads);
@@ -1392,7 +1415,7 @@ int64_t launch_bitslice(const ecamd_map* map, int row0, int nrows, const ApplyAr
     const uint32_t in_records = realign_records(a, K, cover, copy_off != nullptr, shifts);
     hipFunction_t fn = bitslice_function(map->device, sub, nrows, K, form.depth, mode == 2, hold, copy_off != nullptr,
                                          0, wave, &shifts, form.prefetch, nullptr, &form.occ, chk != nullptr,
-                                         chk && chk->suspects);
+                                         chk && chk->suspects, chk ? 0 : form.opts);
     if (!fn) return 0;
     BsArgs b{};
     b.in_base = a.in_base;
@@ -1470,6 +1493,14 @@ int64_t launch_bitslice(const ecamd_map* map, int row0, int nrows, const ApplyAr
                         : shifts.empty() ? static_cast<int>(g_tune.bs_copy_per_cu)
                                          : static_cast<int>(g_tune.bs_copy_realign_per_cu);
         const unsigned lds = cap_lds(fn, wg_cap);
+        if (!chk && (form.opts & kBsOptTimeline)) {  // (only the timeline form's kernel reads these)
+            // tile t of the pass: launches after the first continue the record numbering
+            const uint32_t first = b.tiles_per_stripe * static_cast<uint32_t>(s0);
+            const uint32_t total = g_timeline_records.load(std::memory_order_relaxed);
+            uint32_t* buf = g_timeline.load(std::memory_order_relaxed);
+            c.timeline = buf && total > first ? buf + static_cast<size_t>(first) * 8 : nullptr;
+            c.timeline_records = c.timeline ? total - first : 0;
+        }
         *rc = bitslice_launch(fn, c, static_cast<int>(grid), st, hold, threads, lds);
         if (chk && *rc == 0) (chk->suspects ? g_locate_fused : g_check_fused).fetch_add(1, std::memory_order_relaxed);
     }
@@ -2964,6 +2995,8 @@ int ecamd_tune(const char* key, int value)
         g_tune.bs_wave_depth = value == 2 || value == 4 ? value : 0;
     } else if (k == "bs_tiles_per_slot") {
         g_tune.bs_tiles_per_slot = value >= 0 && value <= (1 << 20) ? value : 16;
+    } else if (k == "bs_store_through") {
+        g_tune.bs_store_through = value < 0 ? -1 : value > 0 ? 1 : 0;
     } else if (k == "xor_tiles_per_slot") {
         g_tune.xor_tiles_per_slot = value >= 0 && value <= (1 << 20) ? value : 32;
     } else if (k == "frame_crc_wave") {  // (negative: the defaults)
@@ -3824,7 +3857,7 @@ int ecamd_bitslice_prebuild(int k, int m, const int* missing, int dest, int rebu
         BsForm f;
         if (!bs_form(nrows, K, false, false, f)) continue;
         const int r = ecamd::bitslice_prebuild(group_rows(fm, row0, nrows), nrows, K, f.depth, false, 0, f.wave, nullptr,
-                                               f.prefetch, f.occ, arch, dir);
+                                               f.prefetch, f.occ, arch, dir, false, false, f.opts);
         if (r < 0) return fail(ECAMD_EHIP, "bitsliced prebuild failed (%d) for a %dx%d map", r, nrows, K);
         built += r;
     }
@@ -3875,7 +3908,7 @@ int ecamd_rs_kernel_form(int k, int m, const int* missing, int dest, int rebuild
             std::shared_ptr<void> hold;
             int st = -1;
             (void)bitslice_function(dev, group_rows(fm, row0, nrows), nrows, K, f.depth, g_tune.bitslice == 2, hold,
-                                    false, 0, f.wave, nullptr, f.prefetch, &st, &f.occ);
+                                    false, 0, f.wave, nullptr, f.prefetch, &st, &f.occ, false, false, f.opts);
             g = st == 1 ? ECAMD_FORM_BITSLICED : st == 0 ? ECAMD_FORM_COMPILING : ECAMD_FORM_UNAVAILABLE;
         }
         if (rank(g) > rank(form)) form = g;
@@ -3907,6 +3940,15 @@ int ecamd_event_elapsed_ms(void* start, void* stop, float* ms)
 {
     HIP_TRY(hipEventSynchronize(static_cast<hipEvent_t>(stop)));
     HIP_TRY(hipEventElapsedTime(ms, static_cast<hipEvent_t>(start), static_cast<hipEvent_t>(stop)));
+    return 0;
+}
+
+int ecamd_bitslice_timeline(void* buf, unsigned records)
+{
+    if (records && !buf) return fail(ECAMD_EINVAL, "null timeline buffer");
+    g_timeline_records.store(0, std::memory_order_relaxed);
+    g_timeline.store(records ? static_cast<uint32_t*>(buf) : nullptr, std::memory_order_relaxed);
+    g_timeline_records.store(records, std::memory_order_relaxed);
     return 0;
 }
 

@@ -210,6 +210,7 @@ struct BsEntry {
     BsOcc occ;                // one-wave form: amdgpu_waves_per_eu and input barrier (bitslice.hpp)
     bool check = false;       // check form (BitsliceStyle::check): plain maps only
     bool locate = false;      // locate form (BitsliceStyle::locate_ratio): a check form with a second stage
+    int opts = 0;             // store policy / timeline of the plain one-wave form (BitsliceStyle::opts)
     int cap_index = 0;    // into kCaps: shared temporaries allowed (fewer: fewer registers)
     std::string arch;     // target of the code object (the requesting device's gcnArchName)
     std::string co_path;  // cache file of the code object
@@ -346,15 +347,40 @@ std::string request_of(const BsEntry& e)
                                 : 0;
     return bitslice_request(e.coeff, e.R, e.K, kCaps[e.cap_index], e.depth, e.copy, e.crc > 0,
                             e.crc > 0 ? (e.crc & 7) : 1, (e.crc & 8) != 0, (e.crc & 16) != 0, e.wave, &e.shifts,
-                            e.prefetch, e.wave || e.occ.threads || cw ? &e.occ : nullptr, cw, e.check, e.locate);
+                            e.prefetch, e.wave || e.occ.threads || cw ? &e.occ : nullptr, cw, e.check, e.locate, e.opts);
 }
-std::string object_name(const BsEntry& e)
+// The part of the generator's identity that belongs to BitsliceStyle::opts, hashed into the names of objects
+// built with any of them only: every other object keeps the name it always had.  The emission sites it covers
+// are marked in host/bitslice.cpp (bitslice_source, `opts`).
+const std::string& opts_fingerprint()
+{
+    static std::string fp;
+    static std::once_flag once;
+    std::call_once(once, [] {
+        const BitsliceNet tiny = bitslice_network({3}, 1, 1, 0);
+        BitsliceStyle st;
+        st.threads = 64;
+        st.waves = 2;
+        st.opts = kBsOptAll;
+        fp = bitslice_source(tiny, 0, st);
+    });
+    return fp;
+}
+std::string object_name_of(const std::string& request, const std::string& arch)
 {
     char name[40];
+    // (asked of the request's own parser, not of its text)
+    std::vector<int> coeff;
+    int R = 0, K = 0, cap = 0, depth = 0, obits = 0;
+    const bool opts = bitslice_parse_request(request, coeff, R, K, cap, depth, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                             nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &obits) &&
+                      obits != 0;
     std::snprintf(name, sizeof(name), "bs_%016llx",
-                  static_cast<unsigned long long>(fnv1a(generator_fingerprint() + "arch " + e.arch + "\n" + request_of(e))));
+                  static_cast<unsigned long long>(fnv1a(generator_fingerprint() + (opts ? opts_fingerprint() : std::string()) +
+                                                        "arch " + arch + "\n" + request)));
     return name;
 }
+std::string object_name(const BsEntry& e) { return object_name_of(request_of(e), e.arch); }
 
 // Start (or skip, when shipped or cached) the build of e's kernel at kCaps[e.cap_index]; queue it
 // (state 2) while max_jobs() compilers run, unless `force`.  Caller holds the lock.
@@ -460,7 +486,7 @@ void wait_compile(std::unique_lock<std::mutex>& lk, const std::shared_ptr<BsEntr
 // kernels get equal requests.  Returns the key.
 std::vector<int> normalize(const std::vector<int>& coeff, int R, int K, int& depth, bool& copy, int& crc,
                            bool& wave, const std::vector<int>* in_shift, int& prefetch, std::vector<int>& shifts,
-                           BsOcc& occ, bool& check, bool& locate)
+                           BsOcc& occ, bool& check, bool& locate, int& opts)
 {
     if (crc) {  // position sets 1 / 2 / 4, + 8 for the lane-shift fold, + 16 for nibble piece tables;
         // + 32 for one-wave tiles (with the lane fold, byte tables) in workgroups of (crc >> 6) waves
@@ -502,6 +528,9 @@ std::vector<int> normalize(const std::vector<int>& coeff, int R, int K, int& dep
         key.insert(key.end(), shifts.begin(), shifts.end());
     }
     if (check) key.push_back(locate ? -3 : -2);  // (no coefficient or shift is negative)
+    // BitsliceStyle::opts: the plain one-wave register form only (as bitslice_request)
+    opts = wave && !copy && !check && depth == 0 ? opts & kBsOptAll : 0;
+    if (opts) key.push_back(-16 - opts);
     return key;
 }
 
@@ -540,7 +569,7 @@ long code_object_scratch(const std::string& code)
 // 0: this form never takes a bitsliced kernel, < 0: the helper is missing or failed.
 int bitslice_prebuild(const std::vector<int>& coeff, int R, int K, int depth, bool copy, int crc, bool wave,
                       const std::vector<int>* in_shift, int prefetch, const BsOcc& occ_in, const std::string& arch,
-                      const std::string& dir, bool check, bool locate)
+                      const std::string& dir, bool check, bool locate, int opts)
 {
     if (R <= 0 || R > kBsMaxR || K <= 0 || K > kBsMaxK) return 0;
     const std::string helper = helper_path();
@@ -548,10 +577,11 @@ int bitslice_prebuild(const std::vector<int>& coeff, int R, int K, int depth, bo
     BsEntry e;
     std::vector<int> shifts;
     BsOcc occ = occ_in;
-    normalize(coeff, R, K, depth, copy, crc, wave, in_shift, prefetch, shifts, occ, check, locate);
+    normalize(coeff, R, K, depth, copy, crc, wave, in_shift, prefetch, shifts, occ, check, locate, opts);
     e.occ = occ;
     e.check = check;
     e.locate = locate;
+    e.opts = opts;
     e.coeff = coeff;
     e.R = R;
     e.K = K;
@@ -600,7 +630,7 @@ int bitslice_prebuild(const std::vector<int>& coeff, int R, int K, int depth, bo
 hipFunction_t bitslice_function(int dev, const std::vector<int>& coeff, int R, int K, int depth, bool wait,
                                 std::shared_ptr<void>& hold, bool copy, int crc, bool wave,
                                 const std::vector<int>* in_shift, int prefetch, int* status, const BsOcc* occ_in,
-                                bool check, bool locate)
+                                bool check, bool locate, int opts)
 {
     if (status) *status = -1;
     if (R <= 0 || R > kBsMaxR || K <= 0 || K > kBsMaxK || (helper_path().empty() && shipped_dir().empty()))
@@ -608,7 +638,7 @@ hipFunction_t bitslice_function(int dev, const std::vector<int>& coeff, int R, i
     std::vector<int> shifts;
     BsOcc occ = occ_in ? *occ_in : BsOcc{};
     const std::vector<int> key = normalize(coeff, R, K, depth, copy, crc, wave, in_shift, prefetch, shifts, occ, check,
-                                           locate);
+                                           locate, opts);
     std::vector<std::shared_ptr<BsEntry>> evicted;  // released after the lock (declared before it)
     std::unique_lock<std::mutex> lk(g_jit_mu);
     for (size_t i = 0; i < g_running.size();) {  // reap finished compilers, freeing their slots
@@ -641,6 +671,7 @@ hipFunction_t bitslice_function(int dev, const std::vector<int>& coeff, int R, i
         slot->occ = occ;
         slot->check = check;
         slot->locate = locate;
+        slot->opts = opts;
         slot->arch = device_arch(dev);
         slot->cap_index = first_cap(R, crc, wave);
         start_compile(slot, wait);
@@ -761,6 +792,14 @@ extern "C" int ecamd_bitslice_entries(void)
 {
     std::lock_guard<std::mutex> lk(ecamd::g_jit_mu);
     return static_cast<int>(ecamd::g_jit.size());
+}
+
+extern "C" int ecamd_bitslice_object_name(const char* request, const char* arch, char* buf, int size)
+{
+    if (!request || !arch || !buf || size <= 0) return -1;
+    const std::string name = ecamd::object_name_of(request, arch);
+    std::snprintf(buf, static_cast<size_t>(size), "%s", name.c_str());
+    return static_cast<int>(name.size());
 }
 
 extern "C" int ecamd_bitslice_available(void) { return ecamd::helper_path().empty() ? 0 : 1; }

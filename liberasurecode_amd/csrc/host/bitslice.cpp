@@ -364,6 +364,12 @@ std::string bitslice_source(const BitsliceNet& net, int depth, BitsliceStyle sty
     const bool locate = !style.locate_ratio.empty() && !style.crc && !style.copy_through && net.R >= 2 && LK >= 1 &&
                         style.locate_ratio.size() == static_cast<size_t>(net.R - 1) * LK;
     const bool check = (style.check || locate) && !style.crc && !style.copy_through;  // plain maps only
+    // store policy and timeline: the plain one-wave register form only.  What `opts` emits (the prelude's tail
+    // below, the stores' aux in outputs(), the stamps and the record in the register form's tile loop) is
+    // covered by opts_fingerprint() in hip/ecamd_jit.hip, NOT by generator_fingerprint(): whoever changes one of
+    // those sites keeps a form with every opts bit in that fingerprint, or cached objects of the old emission
+    // are reused.
+    const int opts = !style.crc && !style.copy_through && !check && !D && style.threads == 64 ? style.opts & kBsOptAll : 0;
     if (check) {
         // the check form's kernarg struct ends with the status words (BsArgs), the locate form's with
         // the suspects after them; every other form keeps the prelude it always had
@@ -379,6 +385,15 @@ std::string bitslice_source(const BitsliceNet& net, int depth, BitsliceStyle sty
         // which the 8 x 28 map of (20,8) has none left for (24 bytes of scratch)
         if (locate)
             s << "__device__ __forceinline__ u32 opq(u32 x)\n{\n    asm volatile(\"\" : \"+s\"(x));\n    return x;\n}\n";
+    } else if (opts & kBsOptTimeline) {
+        // the timeline form's kernarg struct goes on to the end of BsArgs (the check and locate fields are
+        // declared for their place only)
+        std::string pre(kPrelude);
+        const std::string tail = "    i32 crc_nfrag;\n};";
+        pre.replace(pre.find(tail), tail.size(),
+                    "    i32 crc_nfrag;\n    u32* status;\n    u8 status_bit[8];\n    u32* suspects;\n    u8 frag_bit[32];\n"
+                    "    u32* tl;\n    u32 tl_records;\n};");
+        s << pre;
     } else
         s << kPrelude;
     if (style.crc) s << kPreludeCrc;
@@ -580,17 +595,19 @@ std::string bitslice_source(const BitsliceNet& net, int depth, BitsliceStyle sty
                  "        }\n";
             return;
         }
-        s << "#pragma unroll\n        for (int r = 0; r < " << net.R
-          << "; r++) {\n"
-             "            tr16(acc[r]);\n"
-             "#pragma unroll\n"
-             "            for (int c = 0; c < 4; c++) {\n"
-             "                const v4u v = {acc[r][4 * c], acc[r][4 * c + 1], acc[r][4 * c + 2], acc[r][4 * c + 3]};\n"
-             "                __builtin_amdgcn_raw_buffer_store_b128(v, "
-          << rout << ", a.out_off[r] + " << off
-          << " + c * " << CS << ", 0, 2);\n"
-             "            }\n"
-             "        }\n";
+        // aux 2: nt; 19: nt sc0 sc1, a write-through store that leaves no dirty line in L2
+        auto group = [&](int aux) {
+            s << "#pragma unroll\n"
+                 "            for (int c = 0; c < 4; c++) {\n"
+                 "                const v4u v = {acc[r][4 * c], acc[r][4 * c + 1], acc[r][4 * c + 2], acc[r][4 * c + 3]};\n"
+                 "                __builtin_amdgcn_raw_buffer_store_b128(v, "
+              << rout << ", a.out_off[r] + " << off << " + c * " << CS << ", 0, " << aux
+              << ");\n"
+                 "            }\n";
+        };
+        s << "#pragma unroll\n        for (int r = 0; r < " << net.R << "; r++) {\n            tr16(acc[r]);\n";
+        group(opts & kBsOptStoreThrough ? 19 : 2);
+        s << "        }\n";
     };
     if (CW) {
         // crc variant in one-wave tiles: every wave of a workgroup streams 4 KiB tiles on its own -- lane
@@ -893,8 +910,11 @@ std::string bitslice_source(const BitsliceNet& net, int depth, BitsliceStyle sty
         return s.str();
     }
     if (!D) {
-        s << "    for (u32 t = blockIdx.x; t < a.ntiles; t += gridDim.x) {\n"
-             "        const u32 sl = t / a.tiles_per_stripe;\n"
+        s << "    for (u32 t = blockIdx.x; t < a.ntiles; t += gridDim.x) {\n";
+        if (opts & kBsOptTimeline)
+            s << "        const unsigned long long tl0 = __builtin_amdgcn_s_memrealtime();\n"
+                 "        __builtin_amdgcn_sched_barrier(0);\n";
+        s << "        const u32 sl = t / a.tiles_per_stripe;\n"
              "        const u32 s = a.stripe_list ? (u32)a.stripe_list[sl] : sl;\n"
              "        const i32 off = (i32)(t - sl * a.tiles_per_stripe) * "
           << TILE
@@ -1022,6 +1042,16 @@ std::string bitslice_source(const BitsliceNet& net, int depth, BitsliceStyle sty
             s << "        }\n";
         }
         outputs("rout", "off");
+        if (opts & kBsOptTimeline)
+            // the tile ends when its stores have left the wave; one lane writes the record (plain vector
+            // stores, to words nothing else reads)
+            s << "        asm volatile(\"s_waitcnt vmcnt(0)\" ::: \"memory\");\n"
+                 "        const unsigned long long tl1 = __builtin_amdgcn_s_memrealtime();\n"
+                 "        if (threadIdx.x == 0u && t < a.tl_records) {\n"
+                 "            v4u* rec = (v4u*)(a.tl + (unsigned long long)t * 8u);\n"
+                 "            rec[0] = v4u{(u32)tl0, (u32)(tl0 >> 32), (u32)tl1, (u32)(tl1 >> 32)};\n"
+                 "            rec[1] = v4u{t, __builtin_amdgcn_s_getreg(63508), __builtin_amdgcn_s_getreg(63492), 0u};\n"
+                 "        }\n";
         s << "    }\n}\n";
         return s.str();
     }
@@ -1215,9 +1245,12 @@ std::string bitslice_source(const BitsliceNet& net, int depth, BitsliceStyle sty
 std::string bitslice_request(const std::vector<int>& coeff, int R, int K, int cap, int depth, bool copy,
                              bool crc, int crc_pos, bool crc_lane, bool crc_nib, bool wave,
                              const std::vector<int>* in_shift, int prefetch, const BsOcc* occ, int crc_wave,
-                             bool check, bool locate)
+                             bool check, bool locate, int opts)
 {
     std::ostringstream s;
+    // BitsliceStyle::opts: the plain one-wave register form only
+    if (!wave || copy || crc || depth != 0 || check || locate) opts = 0;
+    opts &= kBsOptAll;
     // flags: bit 0 copy-through, bit 1 crc (which copies too), bits 2-3 log2 of the crc position
     // sets, bit 4 lane-shift fold, bit 5 nibble piece tables, bit 6 one-wave tiles (not with crc),
     // bit 7 the register budget of 2 waves per SIMD (set with bit 6: the compiler then keeps the
@@ -1266,13 +1299,15 @@ std::string bitslice_request(const std::vector<int>& coeff, int R, int K, int ca
     // request reads as it always did
     // (the locate form -- a check form with a second stage -- says "locate" in its place)
     if ((check || locate) && !copy && !crc) s << (locate ? "locate\n" : "check\n");
+    // BitsliceStyle::opts likewise: the word and its bits, written only when one is set
+    if (opts) s << "opts " << opts << "\n";
     return s.str();
 }
 
 bool bitslice_parse_request(const std::string& text, std::vector<int>& coeff, int& R, int& K, int& cap,
                             int& depth, bool* copy, bool* crc, int* crc_pos, bool* crc_lane, bool* crc_nib,
                             bool* wave, bool* budget2, std::vector<int>* in_shift, int* prefetch, BsOcc* occ,
-                            int* crc_wave, bool* check, bool* locate)
+                            int* crc_wave, bool* check, bool* locate, int* opts)
 {
     std::istringstream s(text);
     std::string magic;
@@ -1334,12 +1369,57 @@ bool bitslice_parse_request(const std::string& text, std::vector<int>& coeff, in
     for (int& c : coeff)
         if (!(s >> c) || c < 0 || c > 0xffff) return false;
     std::string word;
-    const bool chk = static_cast<bool>(s >> word);
+    bool chk = static_cast<bool>(s >> word);
+    int obits = 0;
+    if (chk && word == "opts") {  // the plain one-wave register form only; never with a check word
+        if (!(s >> obits) || obits <= 0 || obits > kBsOptAll || !(cp & 64) || (cp & 3) || depth != 0) return false;
+        if (s >> word) return false;
+        chk = false;
+    }
+    if (opts) *opts = obits;
     if (chk && ((word != "check" && word != "locate") || (cp & 3))) return false;  // plain maps only
+    std::string more;
+    if (chk && (s >> more)) return false;  // (an opts word after it included)
     const bool loc = chk && word == "locate";
     if (loc && bitslice_locate_ratio(coeff, R, K).empty()) return false;  // >= 2 rows, a non-zero first row
     if (check) *check = chk;
     if (locate) *locate = loc;
+    return true;
+}
+
+bool bitslice_request_style(const std::string& text, std::vector<int>& coeff, int& R, int& K, int& cap, int& depth,
+                            BitsliceStyle& style)
+{
+    bool copy = false, crc = false, crc_lane = false, crc_nib = false, wave = false, budget2 = false;
+    int crc_pos = 1;
+    std::vector<int> shifts;
+    int prefetch = 0;
+    BsOcc occ;
+    int crc_wave = 0;
+    bool check = false, locate = false;
+    int opts = 0;
+    if (!bitslice_parse_request(text, coeff, R, K, cap, depth, &copy, &crc, &crc_pos, &crc_lane, &crc_nib, &wave,
+                                &budget2, &shifts, &prefetch, &occ, &crc_wave, &check, &locate, &opts))
+        return false;
+    style = BitsliceStyle{};
+    style.copy_through = copy;
+    style.crc = crc;
+    style.crc_pos = crc_pos;
+    style.crc_lane = crc_lane;
+    style.crc_nib = crc_nib;
+    style.threads = wave ? 64 : occ.threads ? occ.threads : 256;
+    style.crc_wave = crc_wave & 15;
+    style.crc_mix = (crc_wave & 16) != 0;
+    style.crc_mb = 4 - ((crc_wave >> 5) & 3);
+    style.crc_l1 = (crc_wave >> 7) & 1;
+    style.waves = wave || crc_wave ? occ.wmin : 0;  // one-wave forms: the request's occupancy (0: by R)
+    style.waves_max = wave || crc_wave ? occ.wmax : 0;
+    style.input_barrier = (wave || crc_wave) && occ.barrier;
+    style.in_shift = shifts;
+    style.prefetch = prefetch;
+    style.check = check;
+    if (locate) style.locate_ratio = bitslice_locate_ratio(coeff, R, K);
+    style.opts = opts;
     return true;
 }
 

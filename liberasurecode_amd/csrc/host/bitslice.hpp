@@ -126,7 +126,16 @@ struct BitsliceStyle {
     // own.  A candidate survives when no lane of the wave has a bit left, and one lane ANDs the mask
     // of survivors (bits frag_bit[] of BsArgs; all other bits set) into suspects[stripe].
     std::vector<int> locate_ratio;
+    // plain one-wave register form only: kBsOpt* bits; 0: the form as it always was
+    int opts = 0;
 };
+// BitsliceStyle::opts (the request's trailing "opts" word carries the same bits)
+constexpr int kBsOptStoreThrough = 1;  // the outputs are stored write-through (sc0 sc1, still nt): the lines go
+                                       //   straight to memory instead of being allocated in L2 and evicted later
+constexpr int kBsOptTimeline = 2;      // measurement only: each tile's start / end wall clock, XCC and hardware id
+                                       //   to BsArgs::timeline, which only this form's prelude declares
+                                       //   (tools/launch_timeline.py)
+constexpr int kBsOptAll = 3;
 // ratio[(R - 1) * (K - R)] of the R x K syndrome map [A | I_R] (row-major coeff); empty when R < 2 or
 // an entry of A's first row is zero (no locate form).
 std::vector<int> bitslice_locate_ratio(const std::vector<int>& coeff, int R, int K);
@@ -167,13 +176,17 @@ std::string bitslice_request(const std::vector<int>& coeff, int R, int K, int ca
                              bool crc = false, int crc_pos = 1, bool crc_lane = false, bool crc_nib = false,
                              bool wave = false, const std::vector<int>* in_shift = nullptr, int prefetch = 0,
                              const BsOcc* occ = nullptr, int crc_wave = 0, bool check = false,
-                             bool locate = false);
+                             bool locate = false, int opts = 0);
 bool bitslice_parse_request(const std::string& text, std::vector<int>& coeff, int& R, int& K, int& cap,
                             int& depth, bool* copy = nullptr, bool* crc = nullptr, int* crc_pos = nullptr,
                             bool* crc_lane = nullptr, bool* crc_nib = nullptr, bool* wave = nullptr,
                             bool* budget2 = nullptr, std::vector<int>* in_shift = nullptr,
                             int* prefetch = nullptr, BsOcc* occ = nullptr, int* crc_wave = nullptr,
-                            bool* check = nullptr, bool* locate = nullptr);
+                            bool* check = nullptr, bool* locate = nullptr, int* opts = nullptr);
+// The style ecamd_jitc builds a parsed request in (before its environment's experiment overrides), so
+// that whoever needs a request's source gets the compiler's: false when the text is no valid request.
+bool bitslice_request_style(const std::string& text, std::vector<int>& coeff, int& R, int& K, int& cap, int& depth,
+                            BitsliceStyle& style);
 
 // Kernel arguments (layout shared by the generated source and the launcher).
 constexpr int kBsTile = 16384;  // bytes of each fragment per workgroup tile (256 lanes x 64 B)
@@ -216,6 +229,11 @@ struct BsArgs {
     // candidates it rules out; frag_bit[i] is the fragment index of input i (the checked rows last)
     uint32_t* suspects;
     uint8_t frag_bit[kBsMaxK];
+    // timeline form (kBsOptTimeline; only its generated prelude declares these two): 32-byte records {start,
+    // end (64-bit wall clock), tile, XCC id, hardware id, 0} of tile t at timeline + 8 t, written for
+    // t < timeline_records
+    uint32_t* timeline;
+    uint32_t timeline_records;
 };
 
 }  // namespace ecamd

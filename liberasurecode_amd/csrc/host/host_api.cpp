@@ -274,4 +274,45 @@ int64_t ecamd_bitslice_source(const int* coeff, int R, int K, int cap, int depth
     return static_cast<int64_t>(src.size());
 }
 
+namespace {
+int64_t copy_out(const std::string& text, char* buf, int64_t size)
+{
+    if (buf && size > 0) {
+        const size_t n = std::min(static_cast<size_t>(size - 1), text.size());
+        std::memcpy(buf, text.data(), n);
+        buf[n] = 0;
+    }
+    return static_cast<int64_t>(text.size());
+}
+}  // namespace
+
+int64_t ecamd_bitslice_wave_request(const int* coeff, int R, int K, int cap, int opts, char* buf, int64_t size)
+{
+    if (!coeff || R <= 0 || R > kBsMaxR || K <= 0 || K > kBsMaxK) return -1;
+    const std::vector<int> c(coeff, coeff + static_cast<size_t>(R) * K);
+    BsOcc occ;
+    occ.barrier = true;
+    return copy_out(bitslice_request(c, R, K, cap, 0, false, false, 1, false, false, true, nullptr, 0, &occ, 0, false,
+                                     false, opts),
+                    buf, size);
+}
+
+int ecamd_bitslice_request_opts(const char* request)
+{
+    std::vector<int> c;
+    int R = 0, K = 0, cap = 0, depth = 0;
+    BitsliceStyle style;
+    if (!request || !bitslice_request_style(request, c, R, K, cap, depth, style)) return -1;
+    return style.opts;
+}
+
+int64_t ecamd_bitslice_request_source(const char* request, char* buf, int64_t size)
+{
+    std::vector<int> c;
+    int R = 0, K = 0, cap = 0, depth = 0;
+    BitsliceStyle style;
+    if (!request || !bitslice_request_style(request, c, R, K, cap, depth, style)) return -1;
+    return copy_out(bitslice_source(bitslice_network(c, R, K, cap), depth, style), buf, size);
+}
+
 }  // extern "C"

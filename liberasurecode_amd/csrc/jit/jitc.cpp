@@ -55,37 +55,11 @@ int main(int argc, char** argv)
     ss << in.rdbuf();
     std::vector<int> coeff;
     int R = 0, K = 0, cap = 0, depth = 0;
-    bool copy = false, crc = false, crc_lane = false, crc_nib = false, wave = false, budget2 = false;
-    int crc_pos = 1;
-    std::vector<int> shifts;
-    int prefetch = 0;
-    ecamd::BsOcc occ;
-    int crc_wave = 0;
-    bool check = false, locate = false;
-    if (!ecamd::bitslice_parse_request(ss.str(), coeff, R, K, cap, depth, &copy, &crc, &crc_pos, &crc_lane,
-                                       &crc_nib, &wave, &budget2, &shifts, &prefetch, &occ, &crc_wave, &check,
-                                       &locate)) {
+    ecamd::BitsliceStyle style;  // lazy / barrier: experiments only, the parent's cache key does not see them
+    if (!ecamd::bitslice_request_style(ss.str(), coeff, R, K, cap, depth, style)) {
         std::fprintf(stderr, "ecamd_jitc: bad request %s\n", argv[1]);
         return 2;
     }
-    ecamd::BitsliceStyle style;  // lazy / barrier: experiments only, the parent's cache key does not see them
-    style.copy_through = copy;
-    style.crc = crc;
-    style.crc_pos = crc_pos;
-    style.crc_lane = crc_lane;
-    style.crc_nib = crc_nib;
-    style.threads = wave ? 64 : occ.threads ? occ.threads : 256;
-    style.crc_wave = crc_wave & 15;
-    style.crc_mix = (crc_wave & 16) != 0;
-    style.crc_mb = 4 - ((crc_wave >> 5) & 3);
-    style.crc_l1 = (crc_wave >> 7) & 1;
-    style.waves = wave || crc_wave ? occ.wmin : 0;  // one-wave forms: the request's occupancy (0: by R)
-    style.waves_max = wave || crc_wave ? occ.wmax : 0;
-    style.input_barrier = (wave || crc_wave) && occ.barrier;
-    style.in_shift = shifts;
-    style.prefetch = prefetch;
-    style.check = check;
-    if (locate) style.locate_ratio = ecamd::bitslice_locate_ratio(coeff, R, K);
     if (const char* v = std::getenv("ECAMD_BS_WPE")) style.waves = std::atoi(v);  // experiment only
     if (const char* v = std::getenv("ECAMD_BS_WPE_MAX")) style.waves_max = std::atoi(v);  // experiment only
     if (const char* v = std::getenv("ECAMD_BS_LAZY")) style.lazy_temps = std::atoi(v) != 0;
