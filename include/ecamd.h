@@ -233,12 +233,24 @@ int ecamd_rs_check(int k, int m, const int *missing, const void *base, int64_t s
                    uint32_t *checked, void *stream);
 /* flat_xor_hd, all k+m fragments present: bit k+p when stored parity p differs from the XOR its
  * parity bitmap names (xor_code_encode).  Same layout rules; ECAMD_EINVAL (d_status untouched) when
- * (k, m, hd) is not a code init_xor_hd_code accepts. */
+ * (k, m, hd) is not a code init_xor_hd_code accepts.
+ * Whole tiles run one read-only fused kernel (xor_check_kernel): 128-bit loads of all k+m fragments,
+ * the m syndromes S_p = stored parity p ^ XOR of the data in bitmap p kept in registers, one status
+ * atomic per wave that sees a non-zero syndrome and no write at all for a consistent tile.  Tiles are
+ * 1 KiB (one-wave workgroups, the default: knob "xor_check_threads" 0 or 64) or 4 KiB (256-lane
+ * workgroups: knob 256).  Long batches split into launches of "xor_tiles_per_slot" tiles per slot
+ * with "xor_wgs" (0: 3) slots per CU; the knob counts 4 KiB tiles, so the one-wave form takes four
+ * times as many of its 1 KiB tiles per slot -- the same bytes per launch.  The rest of each fragment,
+ * fragments shorter than a tile, stripes whose last fragment ends 2 GiB or more past the first, and
+ * everything with knob "xor_check_fused" 0 (default 1) take the scratch path described above.  Knob
+ * "bitslice" does not affect flat XOR.  The results are the same on every path. */
 int ecamd_xor_check(int k, int m, int hd, const void *base, int64_t stripe_stride,
                     int64_t frag_stride, int64_t blocksize, int nstripes, uint32_t *d_status,
                     void *stream);
-/* Fused check launches enqueued by this process (tests pin which path ran). */
+/* Fused check launches enqueued by this process (tests pin which path ran): the bitsliced check form
+ * (rs_vand), and xor_check_kernel's check form (flat XOR), each counted on its own. */
 long long ecamd_check_fused_launches(void);
+long long ecamd_xor_check_fused_launches(void);
 /* Build time, as ecamd_bitslice_prebuild: the fused check kernel(s) of (k, m, missing).  Returns the
  * number of code objects present (0: the check takes no bitsliced form), < 0 on error. */
 int ecamd_check_prebuild(int k, int m, const int *missing, const char *arch, const char *dir);
@@ -273,7 +285,12 @@ int ecamd_rs_locate(int k, int m, const int *missing, const void *base, int64_t 
 /* flat_xor_hd, all fragments present: the same rule over the 0/1 parity bitmaps -- data fragment j
  * explains a word iff every parity that contains j has the same syndrome as the first one that does
  * and every other parity has none; parity p iff only its own syndrome is non-zero.  A flat XOR code
- * is not MDS: two bad fragments can leave a (wrong) single suspect. */
+ * is not MDS: two bad fragments can leave a (wrong) single suspect.
+ * As a lookup (ecamd_xor_check_plan, ecamd_host.h): fragment f explains a word iff all its non-zero
+ * syndromes are equal and the set of rows with a non-zero syndrome is sig[f].  Whole tiles run the
+ * locate form of the fused kernel of ecamd_xor_check (same tiles, same knobs): a clean tile costs what
+ * the check costs; a wave that sees a non-zero syndrome applies the rule in registers and issues one
+ * atomic OR and one atomic AND. */
 int ecamd_xor_locate(int k, int m, int hd, const void *base, int64_t stripe_stride, int64_t frag_stride,
                      int64_t blocksize, int nstripes, uint32_t *d_status, uint32_t *d_suspects,
                      void *stream);
@@ -287,8 +304,21 @@ int ecamd_xor_locate(int k, int m, int hd, const void *base, int64_t stripe_stri
 int ecamd_rs_scrub(int k, int m, void *base, int64_t stripe_stride, int64_t frag_stride,
                    int64_t blocksize, int nstripes, uint32_t *d_status, uint32_t *d_suspects,
                    int *n_clean, int *n_repaired, int *n_unlocated, void *stream);
-/* Fused locate launches enqueued by this process (tests pin which path ran). */
+/* The same for flat_xor_hd: ecamd_xor_locate, a wait for `stream`, then ecamd_xor_decode_multi
+ * (decode_parity 1) with the list {f} for every stripe that has exactly one suspect f and the empty
+ * list for every other.  Counts and arrays as ecamd_rs_scrub.  ECAMD_EINVAL, both arrays untouched,
+ * for a code init_xor_hd_code rejects and for an odd blocksize.
+ * A flat XOR code is not MDS: two bad fragments f1 and f2 with the same error in the same word read
+ * as the single fragment f3 whenever sig[f1] ^ sig[f2] == sig[f3] (ecamd_xor_check_plan; (3,3,3) has
+ * such triples).  Scrub then "repairs" towards f3 and leaves a consistent stripe with both errors
+ * in it, as ecamd_rs_scrub does at m == 2. */
+int ecamd_xor_scrub(int k, int m, int hd, void *base, int64_t stripe_stride, int64_t frag_stride,
+                    int64_t blocksize, int nstripes, uint32_t *d_status, uint32_t *d_suspects,
+                    int *n_clean, int *n_repaired, int *n_unlocated, void *stream);
+/* Fused locate launches enqueued by this process (tests pin which path ran): the bitsliced locate
+ * form (rs_vand), and xor_check_kernel's locate form (flat XOR), each counted on its own. */
 long long ecamd_locate_fused_launches(void);
+long long ecamd_xor_locate_fused_launches(void);
 /* Build time, as ecamd_check_prebuild: the fused locate kernel of (k, m, missing).  Returns the number
  * of code objects present (0: no fused form -- fewer than 2 or more than 8 checked fragments, a shape
  * the bitsliced form declines, or a kernel that would need scratch), < 0 on error. */

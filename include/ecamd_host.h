@@ -76,6 +76,16 @@ int ecamd_split_tables(const int *coeff, int R, int K, int row0, int width, int 
  * -1 if the code is not one init_xor_hd_code accepts (xor_hd_code.c:664-693). */
 int ecamd_xor_code_tables(int k, int m, int hd, unsigned int *parity_bms, unsigned int *data_bms);
 
+/* Check / locate plan of a supported (k, m, hd) code (ecamd_xor_check, ecamd_xor_locate, ecamd.h):
+ * sig[f], f < k+m, is the mask of parity rows whose syndrome S_p = stored parity p ^ XOR of the data
+ * in parity bitmap p a bad fragment f disturbs -- for data fragment j the rows p with bit j in parity
+ * bitmap p, for parity p the single bit 1 << p.  Every signature is non-zero and the k+m of a code
+ * are distinct, so one bad fragment is always located: per 16-bit word, fragment f explains the word
+ * iff all its non-zero syndromes are equal and the set of rows with a non-zero syndrome is sig[f].
+ * The accepted codes have m in {3, 5, 6} and k <= 20.  -1 (sig untouched) if the code is not one
+ * init_xor_hd_code accepts. */
+int ecamd_xor_check_plan(int k, int m, int hd, unsigned int *sig /* k+m */);
+
 /* Exact plan of a reference operation on k+m buffers: op 0 = xor_code_encode, 1 = xor_hd_decode
  * (arg = decode_parity), 2 = xor_reconstruct_one (arg = index).  outputs[*nout] are the buffers
  * the reference modifies, sources[i] the bitmask of ORIGINAL buffers whose XOR output i ends up

@@ -66,6 +66,7 @@ def host():
         _proto(h, "ecamd_bitslice_request_source", C.c_int64, [C.c_char_p, C.c_char_p, C.c_int64])
         _proto(h, "ecamd_split_tables", C.c_int,
                [IP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p])
+        _proto(h, "ecamd_xor_check_plan", C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint)])
         _host = h
     return _host
 
@@ -153,7 +154,11 @@ def dev():
                [C.c_int, C.c_int, C.c_int, VP, C.c_int64, C.c_int64, C.c_int64, C.c_int, VP, VP, VP])
         _proto(d, "ecamd_rs_scrub", C.c_int,
                [C.c_int, C.c_int, VP, C.c_int64, C.c_int64, C.c_int64, C.c_int, VP, VP, IP, IP, IP, VP])
+        _proto(d, "ecamd_xor_scrub", C.c_int,
+               [C.c_int, C.c_int, C.c_int, VP, C.c_int64, C.c_int64, C.c_int64, C.c_int, VP, VP, IP, IP, IP, VP])
         _proto(d, "ecamd_locate_fused_launches", C.c_longlong, [])
+        _proto(d, "ecamd_xor_check_fused_launches", C.c_longlong, [])
+        _proto(d, "ecamd_xor_locate_fused_launches", C.c_longlong, [])
         _proto(d, "ecamd_locate_prebuild", C.c_int, [C.c_int, C.c_int, VP, C.c_char_p, C.c_char_p])
         _proto(d, "ecamd_percall_reset", None, [])
         _proto(d, "ecamd_percall_status", C.c_int, [])

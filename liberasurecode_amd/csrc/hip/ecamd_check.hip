@@ -1,5 +1,6 @@
 // ecamd_check.hip -- stripe consistency check, locate and scrub (ecamd_rs_check / ecamd_xor_check,
-// ecamd_rs_locate / ecamd_xor_locate, ecamd_rs_scrub; DESIGN.md "Consistency check", "Locate and scrub").
+// ecamd_rs_locate / ecamd_xor_locate, ecamd_rs_scrub / ecamd_xor_scrub; DESIGN.md "Consistency check",
+// "Locate and scrub").
 //
 // d_status[s]: the checked fragments of stripe s that disagree with its inputs.  d_suspects[s]
 // (locate): the fragments that ALONE explain every disagreement of stripe s.
@@ -7,8 +8,10 @@
 // Fused stage (rs_vand, whole bitsliced tiles; ecamd::check_fused in ecamd_device.hip): the check
 // form of the bitsliced kernel over the syndrome map [A | I] reads the K inputs and the R checked
 // fragments and writes only the status bits of inconsistent stripes; its locate form also ANDs the
-// candidates it rules out away from the suspects.  Generic stage (everything else: tails, small
-// fragments, shapes the bitsliced kernel declines, maps still compiling, knob bitslice 0, flat XOR):
+// candidates it rules out away from the suspects.  Fused stage (flat XOR, whole 4 KiB or 1 KiB tiles;
+// xor_check_kernel below): the syndromes straight from 128-bit loads of all k + m fragments, the same
+// two forms.  Generic stage (everything else: tails, small fragments, shapes the fused kernels
+// decline, maps still compiling, knob bitslice 0, knob xor_check_fused 0):
 // the strided applies compute the expected fragments into the stream context's scratch (slot
 // kCheckScratchSlot, at most kCheckScratchBytes, so long batches go stripe chunk by stripe chunk and
 // long fragments byte range by byte range) and check_compare_kernel / locate_compare_kernel compare
@@ -18,6 +21,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <memory>
 #include <vector>
 
@@ -25,6 +29,7 @@
 #include "ecamd.h"
 #include "ecamd_host.h"
 #include "ecamd_internal.hpp"
+#include "ecamd_isa.hpp"
 
 using namespace ecamd;
 
@@ -183,6 +188,181 @@ __global__ void __launch_bounds__(256) locate_finalize_kernel(const uint32_t* st
     if (s < n) suspects[s] = status[s] ? suspects[s] & participating : 0u;
 }
 
+// ---- flat XOR, fused stage: xor_check_kernel -------------------------------------------------
+constexpr int kXorCheckMaxFrags = 28;  // 7 load groups of 4; the accepted codes have k + m <= 26
+constexpr int kXorCheckMaxRows = 6;    // m of the accepted codes: 3, 5, 6
+struct XorCheckArgs {
+    const uint8_t* base;  // of the launch's first stripe; fragment f of stripe s at base + s*stripe_stride + off32[f]
+    uint32_t* status;     // of the launch's first stripe
+    uint32_t* suspects;   // locate form only
+    int64_t stripe_stride;
+    uint32_t records;  // bytes of a stripe the buffer resource covers: furthest fragment + the covered bytes
+    uint32_t tiles_per_stripe;
+    int32_t nfrags, nrows, k;
+    int32_t off32[kXorCheckMaxFrags];
+    uint32_t masks[kXorCheckMaxRows];  // row p: parity bitmap p | 1 << (k + p), the stored parity folded in
+    uint32_t sig[kXorCheckMaxFrags];   // ecamd_xor_check_plan
+};
+
+// The check (LOCATE false) and locate form of flat XOR over whole tiles, one workgroup per tile of
+// blockDim.x * 16 bytes; grid = tiles_per_stripe * stripes.  The input side of xor_stream_kernel: one
+// buffer resource per stripe, all k + m fragments in unconditional groups of four 128-bit loads (the
+// unused slots of the last group read zeros through an out-of-range offset), inputs unrolled.
+// Syndrome row p accumulates fragment f under the wave-uniform bit f of masks[p] -- the stored parity
+// is fragment k + p of its own row, so S_p = stored parity p ^ XOR of the data in bitmap p comes out of
+// the same v_bitop3 chain: m <= 6 rows of 4 dwords, no LDS, no scratch.
+// Stage 1: one ballot per row; a wave with no non-zero row is done -- no store, no atomic.  The check
+// form ORs the rows' bits into the status.  Stage 2 (locate, dirty waves only, from the registers): a
+// dirty lane keeps the one fragment f with sig[f] == the lane's set of non-zero rows, provided those
+// rows' 16 bytes are equal, else none.  That is the per-word rule of ecamd_xor_check_plan ANDed over
+// the lane's 8 words: a clean word has no non-zero row, so "every dirty word has rows sig[f], all
+// equal" is "the 16-byte rows of sig[f] are equal and every other row is zero".  keep is ANDed across
+// the wave; one lane issues one atomicOr and one atomicAnd (relaxed, agent scope), as
+// locate_compare_kernel ends.
+template <int KG, bool LOCATE>
+__global__ void __launch_bounds__(256) xor_check_kernel(const XorCheckArgs a)
+{
+    typedef unsigned int v4 __attribute__((ext_vector_type(4)));
+    const uint32_t t = blockIdx.x;
+    const uint32_t s = t / a.tiles_per_stripe;
+    const int off = static_cast<int>((t - s * a.tiles_per_stripe) * (blockDim.x * 16u) + threadIdx.x * 16u);
+    const auto rin = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(a.base) + static_cast<int64_t>(s) * a.stripe_stride,
+                                                       0, static_cast<int>(a.records), 0x00020000);
+    v4 syn[kXorCheckMaxRows];
+#pragma unroll
+    for (int r = 0; r < kXorCheckMaxRows; r++) syn[r] = v4{0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int g = 0; g < KG; g++) {
+        v4 x[4];
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const int f = 4 * g + i;
+            const int o = (f < a.nfrags) ? a.off32[f] + off : static_cast<int>(0x80000000u);
+            x[i] = __builtin_amdgcn_raw_buffer_load_b128(rin, o, 0, 2);
+        }
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const int f = 4 * g + i;
+#pragma unroll
+            for (int r = 0; r < kXorCheckMaxRows; r++) {
+                if (r >= a.nrows) break;
+                const uint32_t msk = 0u - ((a.masks[r] >> f) & 1u);  // wave-uniform
+#pragma unroll
+                for (int d = 0; d < 4; d++) syn[r][d] = xor_and(syn[r][d], x[i][d], msk);
+            }
+        }
+    }
+    uint32_t nz = 0u, bits = 0u;  // this lane's non-zero rows; the wave's, as status bits
+#pragma unroll
+    for (int r = 0; r < kXorCheckMaxRows; r++) {
+        if (r >= a.nrows) break;
+        const bool dirty = (syn[r][0] | syn[r][1] | syn[r][2] | syn[r][3]) != 0u;
+        if (dirty) nz |= 1u << r;
+        if (__ballot(dirty) != 0ull) bits |= 1u << (a.k + r);
+    }
+    if (bits == 0u) return;
+    if constexpr (!LOCATE) {
+        if ((threadIdx.x & 63u) == 0u) __hip_atomic_fetch_or(a.status + s, bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    } else {
+        uint32_t keep = 0xffffffffu;
+        if (nz != 0u) {
+            v4 first = v4{0u, 0u, 0u, 0u};
+            bool have = false, equal = true;
+#pragma unroll
+            for (int r = 0; r < kXorCheckMaxRows; r++) {
+                if (!((nz >> r) & 1u)) continue;
+                if (!have) {
+                    first = syn[r];
+                    have = true;
+                } else if (((syn[r][0] ^ first[0]) | (syn[r][1] ^ first[1]) | (syn[r][2] ^ first[2]) | (syn[r][3] ^ first[3])) != 0u) {
+                    equal = false;
+                }
+            }
+            keep = 0u;
+            if (equal)
+                for (int f = 0; f < a.nfrags; f++)
+                    if (a.sig[f] == nz) keep |= 1u << f;
+        }
+        for (int o = 32; o; o >>= 1) keep &= __shfl_xor(keep, o);
+        if ((threadIdx.x & 63u) == 0u) {
+            __hip_atomic_fetch_or(a.status + s, bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_fetch_and(a.suspects + s, keep, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+}
+
+std::atomic<long long> g_xor_check_fused{0}, g_xor_locate_fused{0};
+
+template <bool LOCATE>
+void xor_check_launch(int groups, dim3 grid, dim3 block, hipStream_t st, const XorCheckArgs& a)
+{
+    switch (groups) {  // 2 ((3,3,3): 6 fragments) to 7 ((20,6,4): 26)
+    case 2: hipLaunchKernelGGL((xor_check_kernel<2, LOCATE>), grid, block, 0, st, a); break;
+    case 3: hipLaunchKernelGGL((xor_check_kernel<3, LOCATE>), grid, block, 0, st, a); break;
+    case 4: hipLaunchKernelGGL((xor_check_kernel<4, LOCATE>), grid, block, 0, st, a); break;
+    case 5: hipLaunchKernelGGL((xor_check_kernel<5, LOCATE>), grid, block, 0, st, a); break;
+    case 6: hipLaunchKernelGGL((xor_check_kernel<6, LOCATE>), grid, block, 0, st, a); break;
+    default: hipLaunchKernelGGL((xor_check_kernel<7, LOCATE>), grid, block, 0, st, a); break;
+    }
+}
+
+// Fused stage of ecamd_xor_check or, with d_suspects, of ecamd_xor_locate over the whole tiles of
+// every fragment (fragment f at f*frag_stride; masks: the m parity bitmaps, sig: ecamd_xor_check_plan).
+// Geometry as launch_xor: one-wave workgroups on 1 KiB tiles or 256-lane workgroups on 4 KiB tiles
+// (knob xor_check_threads 64 / 256), one workgroup per tile, long batches as launches of
+// xor_tiles_per_slot tiles (of 4 KiB) per slot with xor_wgs (0: 3) slots per CU.  By default one-wave
+// tiles at every size, where launch_xor takes them from 256 KiB: on clean data they tie with 4 KiB tiles
+// at (10,6,4) x 1 MiB (0.614 against 0.615 ms) and win every repetition at (3,3,3) x 4 KiB (0.473
+// against 0.486 ms; tools/check_bench.py --xor, profiles/xor_check.json).  Returns
+// the bytes of each fragment covered, or 0 with nothing launched when it declines: knob
+// xor_check_fused 0, a fragment shorter than a tile, a stripe the 32-bit buffer offsets cannot span.
+int64_t xor_check_fused(int dev, int k, int m, const uint32_t* masks, const uint32_t* sig, const uint8_t* base,
+                        int64_t stripe_stride, int64_t frag_stride, int64_t blocksize, int nstripes, uint32_t* d_status,
+                        uint32_t* d_suspects, void* stream)
+{
+    const int n = k + m;
+    if (!dev_tune("xor_check_fused") || n <= 4 || n > kXorCheckMaxFrags || m > kXorCheckMaxRows || nstripes <= 0) return 0;
+    const int knob_threads = dev_tune("xor_check_threads");
+    const int threads = knob_threads ? knob_threads : 64;
+    const int64_t tile = static_cast<int64_t>(threads) * 16;
+    const int64_t cover = blocksize / tile * tile;
+    if (cover == 0 || stripe_stride < 0) return 0;
+    if ((n - 1) * frag_stride + blocksize >= (int64_t(1) << 31)) return 0;
+    const uint64_t tps = static_cast<uint64_t>(cover / tile);
+    const int wgs = dev_tune("xor_wgs") > 0 ? dev_tune("xor_wgs") : 3;
+    const uint64_t slots = static_cast<uint64_t>(dev_cu_count(dev)) * static_cast<uint64_t>(wgs);
+    const uint64_t limit = static_cast<uint64_t>(std::max(dev_tune("xor_tiles_per_slot"), 0)) * static_cast<uint64_t>(256 / threads);
+    const int per = launch_stripes(nstripes, tps, slots, limit);
+    if (tps * static_cast<uint64_t>(per) > 0x7fffffffull) return 0;
+    XorCheckArgs a{};
+    a.stripe_stride = stripe_stride;
+    a.records = static_cast<uint32_t>((n - 1) * frag_stride + cover);
+    a.tiles_per_stripe = static_cast<uint32_t>(tps);
+    a.nfrags = n;
+    a.nrows = m;
+    a.k = k;
+    for (int f = 0; f < n; f++) {
+        a.off32[f] = static_cast<int32_t>(f * frag_stride);
+        a.sig[f] = sig[f];
+    }
+    for (int p = 0; p < m; p++) a.masks[p] = masks[p] | (1u << (k + p));
+    const auto st = static_cast<hipStream_t>(stream);
+    for (int s0 = 0; s0 < nstripes; s0 += per) {
+        const int ns = std::min(per, nstripes - s0);
+        a.base = base + s0 * stripe_stride;
+        a.status = d_status + s0;
+        a.suspects = d_suspects ? d_suspects + s0 : nullptr;
+        const dim3 grid(static_cast<unsigned>(tps * static_cast<uint64_t>(ns))), block(static_cast<unsigned>(threads));
+        if (d_suspects)
+            xor_check_launch<true>((n + 3) / 4, grid, block, st, a);
+        else
+            xor_check_launch<false>((n + 3) / 4, grid, block, st, a);
+        HIP_TRY(hipGetLastError());
+        (d_suspects ? g_xor_locate_fused : g_xor_check_fused).fetch_add(1, std::memory_order_relaxed);
+    }
+    return cover;
+}
+
 // What the entry points differ in.  Fragment f of stripe s lies at base + s*stripe_stride +
 // f*frag_stride.
 struct CheckPlan {
@@ -190,7 +370,8 @@ struct CheckPlan {
     const std::vector<int>* A = nullptr;  // R x K over GF(2^16): checked row r = sum of A[r][j] * input j
     // what computes the checked rows into the scratch
     const ecamd_map* map = nullptr;  // rs_vand: ecamd_map_apply_strided; whole tiles take the fused stage
-    std::vector<uint32_t> masks;     // flat XOR: ecamd_xor_apply_strided over the parity bitmaps; never fused
+    std::vector<uint32_t> masks;     // flat XOR: ecamd_xor_apply_strided over the parity bitmaps; whole tiles take
+    std::vector<uint32_t> sig;       //   xor_check_fused with the signatures of ecamd_xor_check_plan
     CheckMap cached;                 // what A and map point into: the cached check map (rs_vand)
     std::vector<int> bitmaps;        // or the parity bitmaps as 0 / 1 (flat XOR)
 };
@@ -345,6 +526,10 @@ int run_check(int dev, const CheckPlan& p, const void* base, int64_t stripe_stri
         // one launch per group of 8 rows; only what EVERY group covered is done
         cover = blocksize;
         for (int row0 = 0; row0 < R && cover >= 0; row0 += 8) cover = std::min(cover, fused(row0, std::min(8, R - row0)));
+    } else if (!p.sig.empty()) {
+        // flat XOR: one launch reads all K + R fragments of a tile and takes the syndromes from the loads
+        cover = xor_check_fused(dev, K, R, p.masks.data(), p.sig.data(), b, stripe_stride, frag_stride, blocksize, nstripes,
+                                d_status, locating ? d_suspects : nullptr, stream);
     }
     if (cover < 0) return static_cast<int>(cover);
     LocateCmpArgs loc{};
@@ -399,6 +584,8 @@ int xor_call(bool locate, int k, int m, int hd, const void* base, int64_t stripe
     if ((rc = check_layout(locate, base, stripe_stride, frag_stride, blocksize, nstripes, d_status, d_suspects))) return rc;
     CheckPlan p;
     p.masks.assign(pb, pb + m);
+    p.sig.resize(static_cast<size_t>(k + m));
+    if (ecamd_xor_check_plan(k, m, hd, p.sig.data()) != 0) return dev_fail(ECAMD_EINVAL, "no check plan: k=%d m=%d hd=%d", k, m, hd);
     for (int j = 0; j < k; j++) p.inputs.push_back(j);
     for (int r = 0; r < m; r++) {
         p.checked.push_back(k + r);
@@ -407,6 +594,41 @@ int xor_call(bool locate, int k, int m, int hd, const void* base, int64_t stripe
     p.A = &p.bitmaps;
     return run_check(dev, p, base, stripe_stride, frag_stride, blocksize, nstripes, d_status, locate ? d_suspects : nullptr,
                      stream);
+}
+
+// The host half of ecamd_rs_scrub and ecamd_xor_scrub, after the locate: a wait for `stream`, both
+// arrays read back, the counts, and -- when a stripe has exactly one suspect -- decode(lists) with
+// lists[2*s..] = {f, -1} for such a stripe and {-1, -1} (the empty list) for every other.
+template <class Decode>
+int scrub_located(const uint32_t* d_status, const uint32_t* d_suspects, int nstripes, int* n_clean, int* n_repaired,
+                  int* n_unlocated, void* stream, Decode&& decode)
+{
+    int clean = 0, repaired = 0, unlocated = 0;
+    if (nstripes > 0) {
+        HIP_TRY(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
+        std::vector<uint32_t> status(static_cast<size_t>(nstripes)), suspects(static_cast<size_t>(nstripes));
+        HIP_TRY(hipMemcpy(status.data(), d_status, status.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(suspects.data(), d_suspects, suspects.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        std::vector<int> lists(static_cast<size_t>(nstripes) * 2, -1);
+        for (int s = 0; s < nstripes; s++) {
+            const uint32_t sus = suspects[static_cast<size_t>(s)];
+            if (!status[static_cast<size_t>(s)])
+                clean++;
+            else if (sus && !(sus & (sus - 1))) {
+                lists[static_cast<size_t>(s) * 2] = __builtin_ctz(sus);
+                repaired++;
+            } else
+                unlocated++;
+        }
+        if (repaired) {
+            const int rc = decode(lists.data());
+            if (rc) return rc;
+        }
+    }
+    if (n_clean) *n_clean = clean;
+    if (n_repaired) *n_repaired = repaired;
+    if (n_unlocated) *n_unlocated = unlocated;
+    return 0;
 }
 
 // The check map of (k, m, missing) planned on the host alone (build time: no device).
@@ -478,32 +700,24 @@ int ecamd_rs_scrub(int k, int m, void* base, int64_t stripe_stride, int64_t frag
     int rc = ecamd_rs_locate(k, m, nullptr, base, stripe_stride, frag_stride, blocksize, nstripes, d_status, d_suspects,
                              nullptr, stream);
     if (rc) return rc;
-    int clean = 0, repaired = 0, unlocated = 0;
-    if (nstripes > 0) {
-        HIP_TRY(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
-        std::vector<uint32_t> status(static_cast<size_t>(nstripes)), suspects(static_cast<size_t>(nstripes));
-        HIP_TRY(hipMemcpy(status.data(), d_status, status.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(suspects.data(), d_suspects, suspects.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        std::vector<int> lists(static_cast<size_t>(nstripes) * 2, -1);  // {f, -1} or the empty list per stripe
-        for (int s = 0; s < nstripes; s++) {
-            const uint32_t sus = suspects[static_cast<size_t>(s)];
-            if (!status[static_cast<size_t>(s)])
-                clean++;
-            else if (sus && !(sus & (sus - 1))) {
-                lists[static_cast<size_t>(s) * 2] = __builtin_ctz(sus);
-                repaired++;
-            } else
-                unlocated++;
-        }
-        if (repaired &&
-            (rc = ecamd_rs_decode_multi(k, m, lists.data(), 2, 1, base, stripe_stride, frag_stride, blocksize, nstripes, stream)))
-            return rc;
-    }
-    if (n_clean) *n_clean = clean;
-    if (n_repaired) *n_repaired = repaired;
-    if (n_unlocated) *n_unlocated = unlocated;
-    return 0;
+    return scrub_located(d_status, d_suspects, nstripes, n_clean, n_repaired, n_unlocated, stream, [&](const int* lists) {
+        return ecamd_rs_decode_multi(k, m, lists, 2, 1, base, stripe_stride, frag_stride, blocksize, nstripes, stream);
+    });
 }
+
+int ecamd_xor_scrub(int k, int m, int hd, void* base, int64_t stripe_stride, int64_t frag_stride, int64_t blocksize,
+                    int nstripes, uint32_t* d_status, uint32_t* d_suspects, int* n_clean, int* n_repaired,
+                    int* n_unlocated, void* stream)
+{
+    int rc = ecamd_xor_locate(k, m, hd, base, stripe_stride, frag_stride, blocksize, nstripes, d_status, d_suspects, stream);
+    if (rc) return rc;
+    return scrub_located(d_status, d_suspects, nstripes, n_clean, n_repaired, n_unlocated, stream, [&](const int* lists) {
+        return ecamd_xor_decode_multi(k, m, hd, lists, 2, 1, base, stripe_stride, frag_stride, blocksize, nstripes, stream);
+    });
+}
+
+long long ecamd_xor_check_fused_launches(void) { return g_xor_check_fused.load(std::memory_order_relaxed); }
+long long ecamd_xor_locate_fused_launches(void) { return g_xor_locate_fused.load(std::memory_order_relaxed); }
 
 int ecamd_locate_prebuild(int k, int m, const int* missing, const char* arch, const char* dir)
 {

@@ -360,6 +360,11 @@ struct Tuning {
                                   //   64 KiB 0.7-3.5% slower, 4 KiB fragments 2% slower (two runs,
                                   //   tools/xor_threads_ab.py, profiles/r03_xor_threads_ab1.log, _ab2.log)
     Knob xor_grid{1};             // xor_stream_kernel: 1 = one workgroup per tile, 0 = resident slots
+    Knob xor_check_fused{1};      // ecamd_xor_check / ecamd_xor_locate: whole tiles through xor_check_kernel
+                                  //   (ecamd_check.hip); 0 = the generic stage only
+    Knob xor_check_threads{0};    // xor_check_kernel: 64 / 256 threads per workgroup = 1 / 4 KiB tiles; 0 = the
+                                  //   default, 64 at every size (measured: xor_check_fused in ecamd_check.hip,
+                                  //   DESIGN.md "Flat XOR: fused check, locate and scrub")
     Knob bs_wave{1};              // ecamd_bs_kernel in one-wave workgroups of 4 KiB tiles (64 lanes x 4
                                   //   chunks 1 KiB apart, built with a 2-wave register budget) instead of
                                   //   4-wave 16 KiB tiles: 1 (default) row groups of bs_wave_min_rows..4
@@ -460,6 +465,10 @@ int dev_fail(int code, const char* fmt, ...)
 int dev_tune(const char* key)
 {
     const std::string k(key);
+    if (k == "xor_check_fused") return g_tune.xor_check_fused;
+    if (k == "xor_check_threads") return g_tune.xor_check_threads;
+    if (k == "xor_tiles_per_slot") return g_tune.xor_tiles_per_slot;
+    if (k == "xor_wgs") return g_tune.xor_wgs;
     if (k == "crc_bits") return g_tune.crc_bits;
     if (k == "crc_wgs") return g_tune.crc_wgs;
     if (k == "frame_copy_grid") return g_tune.frame_copy_grid;
@@ -502,6 +511,14 @@ int dev_tune(const char* key)
     if (k == "frame_crc_pos") return g_tune.frame_crc_pos;
     if (k == "bitslice_entries") return g_tune.bitslice_entries;
     return 0;
+}
+
+int launch_stripes(int nstripes, uint64_t tiles_per_stripe, uint64_t slots, uint64_t limit)
+{
+    const uint64_t ntiles = tiles_per_stripe * static_cast<uint64_t>(nstripes);
+    if (!limit || ntiles <= limit * slots) return nstripes;
+    const uint64_t launches = (ntiles + limit * slots - 1) / (limit * slots);
+    return static_cast<int>((static_cast<uint64_t>(nstripes) + launches - 1) / launches);
 }
 
 }  // namespace ecamd
@@ -1122,12 +1139,7 @@ template <class Launch>
 int for_each_launch(const ApplyArgs& a, int nstripes, uint64_t tiles_per_stripe, uint64_t slots,
                     uint64_t limit, Launch&& launch)
 {
-    const uint64_t ntiles = tiles_per_stripe * static_cast<uint64_t>(nstripes);
-    int per = nstripes;
-    if (limit && ntiles > limit * slots) {
-        const uint64_t launches = (ntiles + limit * slots - 1) / (limit * slots);
-        per = static_cast<int>((static_cast<uint64_t>(nstripes) + launches - 1) / launches);
-    }
+    const int per = launch_stripes(nstripes, tiles_per_stripe, slots, limit);
     for (int s0 = 0; s0 < nstripes; s0 += per) {
         ApplyArgs c = a;
         if (a.stripe_list) {
@@ -2955,6 +2967,10 @@ int ecamd_tune(const char* key, int value)
         g_tune.frame_copy_u = value == 1 || value == 4 ? value : 0;
     } else if (k == "xor_threads") {
         g_tune.xor_threads = value == 64 || value == 128 || value == 256 ? value : 0;  // else by shape
+    } else if (k == "xor_check_fused") {
+        g_tune.xor_check_fused = value != 0;  // < 0: the default (1)
+    } else if (k == "xor_check_threads") {
+        g_tune.xor_check_threads = value == 64 || value == 256 ? value : 0;  // else the default (64)
     } else if (k == "xor_grid") {
         g_tune.xor_grid = value != 0;  // < 0: the default (1)
     } else if (k == "bs_wave") {

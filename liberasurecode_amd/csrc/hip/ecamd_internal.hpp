@@ -39,6 +39,10 @@ int dev_ensure(int* dev_out);                       // 0, or ECAMD_ENODEV / ECAM
 int dev_cu_count(int dev);
 int dev_fail(int code, const char* fmt, ...);       // sets ecamd_last_error(), returns code
 int dev_tune(const char* key);                      // current value of an ecamd_tune() knob
+// Stripes per launch of a strided pass split into launches of at most `limit` tiles per resident
+// workgroup (`slots` of them), as even as the stripes allow; limit 0: one launch (for_each_launch in
+// ecamd_device.hip, xor_check_fused in ecamd_check.hip).
+int launch_stripes(int nstripes, uint64_t tiles_per_stripe, uint64_t slots, uint64_t limit);
 
 // rs_vand encode whose k data inputs are read from objects (input j of stripe s at
 // obj + s*obj_stride + j*bs) and copied into payload j while the parity is computed

@@ -135,6 +135,19 @@ int ecamd_xor_code_tables(int k, int m, int hd, unsigned int* parity_bms, unsign
     return 0;
 }
 
+int ecamd_xor_check_plan(int k, int m, int hd, unsigned int* sig)
+{
+    XorCode c;
+    if (!sig || !xor_code_lookup(k, m, hd, c)) return -1;
+    for (int j = 0; j < k; j++) {
+        sig[j] = 0;
+        for (int p = 0; p < m; p++)
+            if ((c.parity_bms[p] >> j) & 1u) sig[j] |= 1u << p;
+    }
+    for (int p = 0; p < m; p++) sig[k + p] = 1u << p;
+    return 0;
+}
+
 int ecamd_xor_plan(int op, int k, int m, int hd, const unsigned int* parity_bms,
                    const unsigned int* data_bms, const int* missing, int arg, int* outputs,
                    uint64_t* sources, int* nout)

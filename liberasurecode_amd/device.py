@@ -229,6 +229,20 @@ def rs_scrub(k, m, lay: Layout, stream=None):
     return status, suspects, tuple(c.value for c in counts)
 
 
+def xor_scrub(k, m, hd, lay: Layout, stream=None):
+    """ecamd_xor_scrub on full flat_xor_hd stripes: locate, then repair in place every stripe with
+    exactly one suspect.  Returns (status, suspects, (n_clean, n_repaired, n_unlocated)) as rs_scrub;
+    waits for `stream`, so the repairs are complete on return.  flat_xor_hd is not MDS: two bad
+    fragments can read as a third, which is then "repaired" (include/ecamd.h)."""
+    counts = [C.c_int(0), C.c_int(0), C.c_int(0)]
+    status, suspects = _status_suspects(lambda d, u: dev().ecamd_xor_scrub(
+        k, m, hd, lay.buf.ptr, lay.stripe_stride, lay.frag_stride, lay.blocksize, lay.nstripes, d, u,
+        C.byref(counts[0]), C.byref(counts[1]), C.byref(counts[2]), _s(stream)), lay, stream, "xor_scrub")
+    if stream is None:
+        check(dev().ecamd_synchronize(), "synchronize")
+    return status, suspects, tuple(c.value for c in counts)
+
+
 class GF16Map:
     """An arbitrary R x K GF(2^16) fragment map prepared on the device."""
 

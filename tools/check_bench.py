@@ -15,13 +15,24 @@ the fused locate on a clean batch -- the same loads and network; locate adds one
 launch -- and (b) both on an all-dirty batch, fragment 3 of every stripe rewritten with other data so
 that every wave of every tile takes the second stage.  The VGPR and scratch figures of the shipped
 (10,4) and (20,8) locate objects are read from freshly built code objects when llvm-readelf is there.
-`--parent-check-ms X` records the parent commit's fused check time of the same session."""
+`--parent-check-ms X` records the parent commit's fused check time of the same session.
+
+`--xor` measures flat XOR instead, per shape of `--xor-shapes` ((10,6,4) at 1 MiB x 256 stripes and
+(3,3,3) at 4 KiB x 131072 by default): alternating repetitions of (a) ecamd_xor_encode and ecamd_xor_check /
+ecamd_xor_locate on (b) the generic path (knob xor_check_fused 0, which is what ran before the fused
+kernel existed) and (c) each tile form of the fused kernel (knob xor_check_threads 256, 64 and 0, the
+default), on clean data and then on an all-dirty batch (data fragment 1 of every stripe rewritten).
+The bar for (c) on clean data is (a)'s mean plus the spread of (a)'s own repetitions.  `--tree DIR` runs
+the tool against the package and built libraries of another checkout: with the parent commit's, `--xor`
+gives (a) and (b) as that commit runs them (it has the generic path alone)."""
 import argparse
 import json
 import os
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if "--tree" in sys.argv[1:-1]:  # the package and libraries of another built checkout (before the imports below)
+    ROOT = os.path.abspath(sys.argv[sys.argv.index("--tree") + 1])
 sys.path.insert(0, ROOT)
 import torch  # noqa: E402,F401
 
@@ -172,9 +183,98 @@ def run_locate(d, st, reps, n):
     return out
 
 
+XOR_FORMS = (("generic", 0, 0), ("fused_4k", 1, 256), ("fused_1k", 1, 64), ("fused_default", 1, 0))
+
+
+def run_xor(d, st, k, m, hd, F, S, reps, n):
+    """One flat XOR shape: (a) ecamd_xor_encode, then check and locate on the generic path and on each
+    tile form of the fused kernel, alternating; then the same on an all-dirty batch.  A tree from before
+    the fused kernel (--tree) has the generic path alone: its rows are (a) and (b)."""
+    fused_tree = hasattr(d, "ecamd_xor_check_fused_launches")
+    forms = XOR_FORMS if fused_tree else XOR_FORMS[:1]
+    lay = D.Layout.alloc(k + m, F, S)
+    lay.fill_splitmix(nfrags=k, stream=st)
+    words = D.DeviceBuffer(8 * S)
+    args = (k, m, hd, lay.buf.ptr, lay.stripe_stride, lay.frag_stride, F, S)
+
+    def encode():
+        D.xor_encode(k, m, hd, lay, stream=st)
+
+    def check():
+        _lib.check(d.ecamd_xor_check(*args, words.ptr, st.handle), "xor_check")
+
+    def locate():
+        _lib.check(d.ecamd_xor_locate(*args, words.ptr, words.ptr + 4 * S, st.handle), "xor_locate")
+
+    def form(fused, threads):
+        if not fused_tree:
+            return
+        d.ecamd_tune(b"xor_check_fused", fused)
+        d.ecamd_tune(b"xor_check_threads", threads)
+
+    def round_of(ms, suffix):
+        for name, fused, threads in forms:
+            form(fused, threads)
+            count = (lambda: (d.ecamd_xor_check_fused_launches(), d.ecamd_xor_locate_fused_launches())) if fused_tree \
+                else (lambda: (0, 0))
+            c0, l0 = count()
+            few = n if fused else max(2, n // 4)
+            ms.setdefault("check_%s_%s" % (name, suffix), []).append(timed(st, check, few))
+            ms.setdefault("locate_%s_%s" % (name, suffix), []).append(timed(st, locate, few))
+            c1, l1 = count()
+            assert (c1 > c0, l1 > l0) == (bool(fused), bool(fused)), (name, c1 - c0, l1 - l0)
+
+    encode()
+    for name, fused, threads in forms:  # every path once: results, and the scratch allocated outside the timing
+        form(fused, threads)
+        locate()
+        st.synchronize()
+        assert not words.download().any(), "encoded stripes must read clean (%s)" % name
+    for _ in range(60):  # settle the clocks
+        encode()
+    st.synchronize()
+    algo = S * (k + m) * F
+    ms = {"encode": []}
+    for _ in range(reps):
+        ms["encode"].append(timed(st, encode, n))
+        round_of(ms, "clean")
+    # all-dirty: data fragment 1 of every stripe holds other data, so every word of every tile disagrees
+    _lib.check(d.ecamd_fill_splitmix(lay.buf.ptr + lay.frag_stride, lay.stripe_stride, lay.frag_stride, 1, F, S, 0,
+                                     0x5EED, st.handle), "fill")
+    pb = (_lib.C.c_uint * m)()
+    assert _lib.host().ecamd_xor_code_tables(k, m, hd, pb, None) == 0
+    rows = sum(1 << p for p in range(m) if pb[p] >> 1 & 1)  # the parities that contain data fragment 1
+    for name, fused, threads in forms:
+        form(fused, threads)
+        locate()
+        st.synchronize()
+        got = words.download().view("uint32")
+        assert (got[:S] == rows << k).all() and (got[S:] == 1 << 1).all(), "every stripe must name fragment 1 (%s)" % name
+    for _ in range(reps):
+        round_of(ms, "dirty")
+    form(-1, 0)
+    out = {"k": k, "m": m, "hd": hd, "fragment_bytes": F, "stripes": S, "algorithmic_bytes": algo}
+    out.update({name: series(v, algo) for name, v in ms.items()})
+    enc = out["encode"]
+    out["bar_ms"] = round(enc["mean_ms"] + enc["spread_ms"], 4)  # (a) plus the spread of its own repetitions
+    for name in [f[0] for f in forms[1:]]:
+        for op in ("check", "locate"):
+            c = out["%s_%s_clean" % (op, name)]
+            g = out["%s_generic_clean" % op]
+            out["%s_%s_clean_within_bar" % (op, name)] = bool(c["mean_ms"] <= out["bar_ms"])
+            out["%s_%s_clean_over_generic" % (op, name)] = round(c["mean_ms"] / g["mean_ms"], 4)
+    lay.buf.free()
+    words.free()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--locate", action="store_true", help="measure ecamd_rs_locate at C3 instead")
+    ap.add_argument("--xor", action="store_true", help="measure ecamd_xor_check / ecamd_xor_locate instead")
+    ap.add_argument("--xor-shapes", default="10,6,4,1048576,256;3,3,3,4096,131072",
+                    help="k,m,hd,fragment bytes,stripes; ...")
+    ap.add_argument("--tree", default=None, help="run against the package and libraries of another built checkout")
     ap.add_argument("--parent-check-ms", type=float, default=None)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--n", type=int, default=20)
@@ -187,6 +287,17 @@ def main():
     d = _lib.dev()
     st = D.Stream()
     per_cu = [int(x) for x in a.per_cu.split(",") if x.strip()]
+    if a.xor:
+        doc = {"tool": "tools/check_bench.py --xor", "fused_kernel": hasattr(d, "ecamd_xor_check_fused_launches"), "reps": a.reps, "calls_per_rep": a.n, "shapes": []}
+        for shape in a.xor_shapes.split(";"):
+            k, m, hd, F, S = (int(x) for x in shape.split(","))
+            doc["shapes"].append(run_xor(d, st, k, m, hd, F, S, a.reps, a.n))
+        text = json.dumps(doc, indent=1)
+        print(text)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write(text + "\n")
+        return
     if a.locate:
         doc = {"tool": "tools/check_bench.py --locate", "reps": a.reps, "calls_per_rep": a.n,
                "c3": run_locate(d, st, a.reps, a.n)}
