@@ -263,7 +263,8 @@ int ecamd_check_prebuild(int k, int m, const int *missing, const char *arch, con
  * missing and decode.  Zero: more than one fragment is bad.  Bits of missing fragments and bits
  * >= k+m are never set.  Only these two arrays are written; asynchronous on stream.
  * How much can be told depends on R, the number of checked fragments (m minus the missing ones):
- *   R >= 3  one bad fragment is located; any two bad fragments leave no suspect.
+ *   R >= 3  one bad fragment is located; any two bad fragments leave no suspect (with R >= 4,
+ *           ecamd_rs_locate_pairs below names the two).
  *   R == 2  one bad fragment is located; two bad fragments can in principle be attributed to a
  *           third (a single suspect that is wrong) -- the code corrects one error with two checks
  *           and cannot also detect a second.
@@ -282,6 +283,51 @@ int ecamd_check_prebuild(int k, int m, const int *missing, const char *arch, con
 int ecamd_rs_locate(int k, int m, const int *missing, const void *base, int64_t stripe_stride,
                     int64_t frag_stride, int64_t blocksize, int nstripes, uint32_t *d_status,
                     uint32_t *d_suspects, uint32_t *checked, void *stream);
+/* ---- two bad fragments per stripe (rs_vand only) ----
+ * ecamd_rs_locate_pairs does everything ecamd_rs_locate does -- d_status, d_suspects and *checked are
+ * byte-identical to what that call writes for the same data -- and, in the same asynchronous call
+ * (no host wait), fills d_pairs (nstripes uint32, device memory).  d_pairs[s] is 0 unless
+ * d_status[s] != 0, d_suspects[s] == 0 and R >= 4; for such a stripe it has exactly the two bits
+ * {a, b} when {a, b} is the ONE pair of participating fragments (inputs and checked) that explains
+ * every dirty word, else 0.  A pair explains a word when the word's syndrome vector (S_0..S_{R-1})
+ * lies in the span of columns a and b of the R x (K+R) syndrome matrix [A | I] (A: the check map of
+ * ecamd_rs_check_map, ecamd_host.h).  Four checks determine two unknown error positions:
+ *   R >= 5  two bad fragments are located; any three bad fragments leave no pair.
+ *   R == 4  two bad fragments are located; three bad fragments can in principle be attributed to a
+ *           pair (a pair that is wrong) -- the code corrects two errors with four checks and cannot
+ *           also detect a third.  This is what R == 2 is to ecamd_rs_locate.
+ *   R <  4  d_pairs is all zero.
+ * The pair is unique because any four columns of [A | I] are linearly independent; the plan
+ * (ecamd_rs_locate_pairs_map, ecamd_host.h) verifies that once per (k, m, missing) and keeps the
+ * result with the cached check map.  For a map where it does not hold, d_pairs is all zero: uniqueness
+ * would not be a theorem.  (It holds for every rs_vand map that was tried.)
+ * ECAMD_EINVAL as for ecamd_rs_locate, an odd blocksize included, and also for a null d_pairs; all
+ * three arrays are then untouched.  Exactly nstripes words of each array are written.
+ * The pair stage runs after the locate, on its results and on the same stream: d_pairs set to 0 (by
+ * the locate's own last kernel), locate_pairs_kernel, a finalize.  Its workgroups load d_status[s] and d_suspects[s] and go on only
+ * for a dirty stripe without a suspect, whose K inputs and R checked fragments they read again -- no
+ * scratch -- taking the syndromes by shift and xor: a clean batch costs two loads per workgroup, a
+ * batch of damaged pairs several times its locate (DESIGN.md "Two bad fragments").  Knob
+ * "pairs_grid" > 0 caps both grid dimensions (tests); like every knob it does not change results. */
+int ecamd_rs_locate_pairs(int k, int m, const int *missing, const void *base, int64_t stripe_stride,
+                          int64_t frag_stride, int64_t blocksize, int nstripes, uint32_t *d_status,
+                          uint32_t *d_suspects, uint32_t *d_pairs, uint32_t *checked, void *stream);
+/* Scrub FULL stripes in place, two bad fragments included (m >= 4, else ECAMD_EINVAL with the arrays
+ * untouched): ecamd_rs_locate_pairs, a wait for `stream`, then ONE ecamd_rs_decode_multi
+ * (missing_stride 3, rebuild_parity 1) with the list {f} for a stripe with exactly one suspect f,
+ * {a, b} for a stripe with a pair, and the empty list for every other.  The counts (host, may be
+ * NULL) are final on return: consistent stripes, stripes repaired from one suspect, stripes repaired
+ * from a pair, and dirty stripes with neither, which are not written.  The repair launches are
+ * enqueued on stream; the three arrays keep what the locate found.  At m == 4 a pair repair uses up
+ * every check: nothing is left to notice a third bad fragment (see R == 4 above), as ecamd_rs_scrub
+ * at m == 2. */
+int ecamd_rs_scrub_pairs(int k, int m, void *base, int64_t stripe_stride, int64_t frag_stride,
+                         int64_t blocksize, int nstripes, uint32_t *d_status, uint32_t *d_suspects,
+                         uint32_t *d_pairs, int *n_clean, int *n_repaired, int *n_repaired_pairs,
+                         int *n_unlocated, void *stream);
+/* Launches of locate_pairs_kernel enqueued by this process (tests pin that it ran, or did not). */
+long long ecamd_locate_pairs_launches(void);
+
 /* flat_xor_hd, all fragments present: the same rule over the 0/1 parity bitmaps -- data fragment j
  * explains a word iff every parity that contains j has the same syndrome as the first one that does
  * and every other parity has none; parity p iff only its own syndrome is non-zero.  A flat XOR code

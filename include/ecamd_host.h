@@ -17,6 +17,9 @@
  *                                     k: what the inputs imply it holds (no reference counterpart)
  *   ecamd_rs_locate_map               the check map with each column's ratios to its first row: which
  *                                     single fragment explains a syndrome (no reference counterpart)
+ *   ecamd_rs_locate_pairs_map         the check map with, for every pair of columns of [A | I], two pivot
+ *                                     rows and the rows' combinations of them: which two fragments
+ *                                     explain a syndrome (no reference counterpart)
  *   ecamd_rs_reconstruct_map          coefficient row of liberasurecode_rs_vand_reconstruct
  *                                     (liberasurecode_rs_vand.c:483-558)
  */
@@ -64,6 +67,24 @@ int ecamd_rs_check_map(const int *G, int k, int m, const int *missing, int *inpu
  * Every entry of a check map of this code is non-zero.  -1 if more than m missing. */
 int ecamd_rs_locate_map(const int *G, int k, int m, const int *missing, int *inputs, int *checked,
                         int *coeff, int *ncheck, int *ratio);
+
+/* Pair plan (ecamd_rs_locate_pairs, ecamd.h): what ecamd_rs_check_map returns, plus what names the TWO
+ * bad fragments of a stripe.  The participants are the k inputs (0..k-1), then the *ncheck checked
+ * rows (k..k+*ncheck-1); participant c has column c of the syndrome matrix [coeff | I].  With R =
+ * *ncheck >= 4 there are *npairs = P(P-1)/2 pairs a < b of the P = k + R participants, in the order
+ * (0,1), (0,2), ..., (P-2,P-1).  For pair i: pivots[2i], pivots[2i+1] = two rows (p, q) whose 2 x 2 minor
+ * of columns a, b is non-singular, and L[(i*R + r)*2 + 0..1] with
+ *     S_r == L[r][0] * S_p ^ L[r][1] * S_q   for every row r
+ * exactly when the syndrome (S_0..S_{R-1}) of a word lies in the span of columns a and b; rows p and q
+ * of L are (1,0) and (0,1).  A pair whose two columns are linearly dependent is never tested: its
+ * pivots are (-1, -1) and its L rows zero.  *independent4 is 1 when any four columns of [coeff | I]
+ * are linearly independent (every check map of this code that was tried; at most C(32,4) rank
+ * computations): a word that needs two columns then lies in the span of no other pair, so the pair
+ * that explains every dirty word of a stripe is unique.  With R < 4 there is no plan: *npairs 0,
+ * *independent4 0, pivots and L (may be NULL) untouched.  -1 if more than m missing. */
+int ecamd_rs_locate_pairs_map(const int *G, int k, int m, const int *missing, int *inputs, int *checked,
+                              int *coeff, int *ncheck, int *npairs, int *pivots, int *L,
+                              int *independent4);
 
 /* LDS split-table image for rows [row0,row0+width) x inputs [col0,col0+ncols) of the R x K
  * matrix coeff; width in {2,4,8}.  Returns the byte count written (ncols*512*width*2). */

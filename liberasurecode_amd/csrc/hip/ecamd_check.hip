@@ -18,6 +18,11 @@
 // them with the stored ones.  Both stages OR into the same status words and AND into the same
 // suspects, which run_check sets first; locate_finalize_kernel masks the suspects with the
 // participating fragments and clears them on clean stripes -- all on the caller's stream, in order.
+//
+// Pair stage (ecamd_rs_locate_pairs, ecamd_rs_scrub_pairs; rs_vand with R >= 4 checked fragments):
+// after the finalize, locate_pairs_kernel reads the dirty stripes that have no suspect again and ORs
+// into d_pairs[s] the fragments its words need; pairs_finalize_kernel keeps a word of exactly two
+// bits (DESIGN.md "Two bad fragments").
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -180,12 +185,221 @@ __global__ void __launch_bounds__(256) locate_compare_kernel(LocateCmpArgs a)
     }
 }
 
-// suspects[s] = status[s] ? suspects[s] & participating : 0 (the last step of a locate call).
+// suspects[s] = status[s] ? suspects[s] & participating : 0 (the last step of a locate call); with
+// `pairs` (ecamd_rs_locate_pairs) it also sets pairs[s] to 0 for the pair stage that follows.
 __global__ void __launch_bounds__(256) locate_finalize_kernel(const uint32_t* status, uint32_t* suspects,
-                                                              uint32_t participating, int n)
+                                                              uint32_t participating, int n, uint32_t* pairs)
 {
     const int s = static_cast<int>(blockIdx.x) * 256 + static_cast<int>(threadIdx.x);
-    if (s < n) suspects[s] = status[s] ? suspects[s] & participating : 0u;
+    if (s < n) {
+        suspects[s] = status[s] ? suspects[s] & participating : 0u;
+        if (pairs) pairs[s] = 0u;
+    }
+}
+
+// ---- rs_vand, two bad fragments: locate_pairs_kernel (ecamd_rs_locate_pairs) -------------------
+// Runs after a locate, on its results: a stripe that is dirty and has no suspect is read again, the
+// K inputs and the R checked fragments directly (no scratch), 4 bytes -- two words -- per lane at a
+// time.  The participants are the K inputs, then the R checked rows; the table (PairsTable,
+// ecamd_internal.hpp) holds what tests one of them and what tests a pair.
+constexpr int kPairsMaxRows = 31;  // K + R <= 32; R >= 4 leaves K <= 28
+struct PairsArgs {
+    const uint8_t* base;  // participant c of stripe s at base + s*stripe_stride + off[c]
+    const uint32_t* status;
+    const uint32_t* suspects;
+    uint32_t* pairs;
+    const uint32_t* table;
+    int64_t stripe_stride;
+    int64_t len;  // bytes per fragment, even
+    int64_t off[32];
+    uint32_t cmask[kPairsMaxRows * 16];  // [r*16 + b]: the inputs j whose A[r][j] has bit b
+    int32_t nstripes, K, R, singles, npairs, stride;
+};
+
+// Unit u (4 bytes) of a fragment; the last, partial unit byte by byte and zero-padded, so nothing
+// past `len` is ever read.
+__device__ __forceinline__ uint32_t pairs_unit(const uint8_t* x, int64_t u, int64_t whole, int64_t len)
+{
+    if (u < whole) return *reinterpret_cast<const uint32_t*>(x + u * 4);
+    uint32_t w = 0u;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const int64_t q = (whole << 2) + i;
+        if (q < len) w |= static_cast<uint32_t>(x[q]) << (8 * i);
+    }
+    return w;
+}
+
+// Does the single participant of table entry e explain the lane's unit (syndrome row r at syn[r*256],
+// non-zero rows nz)?  Exactly the rows of its column are non-zero and proportional to the pivot row.
+__device__ __forceinline__ bool pairs_single_ok(const uint32_t* e, const uint32_t* syn, int R, uint32_t nz)
+{
+    if (e[1] != nz) return false;
+    const int p = static_cast<int>((e[0] >> 16) & 0xffu);
+    const uint32_t sp = syn[p * 256];
+    for (int r = 0; r < R; r++) {
+        if (r == p || !((nz >> r) & 1u)) continue;
+        if (gf16_mul2(e[2 + r] & 0xffffu, sp) != syn[r * 256]) return false;
+    }
+    return true;
+}
+
+// Does the pair of table entry e explain it?  S_r == L[r][0]*S_p ^ L[r][1]*S_q for every other row.
+__device__ __forceinline__ bool pairs_pair_ok(const uint32_t* e, const uint32_t* syn, int R)
+{
+    const int p = static_cast<int>((e[0] >> 16) & 0xffu), q = static_cast<int>(e[0] >> 24);
+    const uint32_t sp = syn[p * 256], sq = syn[q * 256];
+    for (int r = 0; r < R; r++) {
+        if (r == p || r == q) continue;
+        const uint32_t l = e[2 + r];
+        if ((gf16_mul2(l & 0xffffu, sp) ^ gf16_mul2(l >> 16, sq)) != syn[r * 256]) return false;
+    }
+    return true;
+}
+
+__device__ __forceinline__ uint32_t pairs_bits(uint32_t w) { return (1u << (w & 0x1fu)) | (1u << ((w >> 8) & 0x1fu)); }
+
+// grid (chunks, stripe slots), grid-stride over both; K <= 4*KG.  A workgroup loads status[s] and
+// suspects[s] and goes on only for a dirty stripe without a suspect: on a clean batch every
+// workgroup ends after these two loads per stripe.  Per unit: the K inputs in registers, syndrome
+// row r = stored row r ^ sum_j A[r][j] * input j in Horner form over the coefficient bits (XOR the
+// inputs whose coefficient has bit b -- wave-uniform masks from the arguments --, double, 16 times),
+// the R rows in LDS (row r of lane t at [r*256 + t]; each lane reads only its own).  A dirty unit
+// ORs into the lane's mask: 1 << a when single participant a explains it; else both bits of the
+// workgroup's hint pair when that explains it; else those of the first pair of the table that does,
+// which becomes the hint; else all ones.  One atomicOr per wave with a non-zero mask (relaxed, agent
+// scope); pairs_finalize_kernel keeps a word of exactly two bits.  With any four columns of [A | I]
+// independent (the table exists only then) the pairs that explain a word are every pair that
+// contains one participant, exactly one pair, or none -- so the OR over the dirty units has exactly
+// two bits iff one pair explains them all, whichever of a word's pairs the hint made a lane take.
+// The hint is reset per stripe, between barriers every lane of the workgroup reaches.
+template <int KG>
+__global__ void __launch_bounds__(256) locate_pairs_kernel(const PairsArgs a)
+{
+    extern __shared__ uint32_t pairs_lds[];  // R rows of 256 syndromes, the hint
+    uint32_t* syn = pairs_lds + threadIdx.x;
+    uint32_t* hint = pairs_lds + a.R * 256;
+    const int64_t whole = a.len >> 2, units = (a.len + 3) >> 2;
+    for (int s = static_cast<int>(blockIdx.y); s < a.nstripes; s += static_cast<int>(gridDim.y)) {
+        if (a.status[s] == 0u || a.suspects[s] != 0u) continue;  // the same for every lane
+        if (threadIdx.x == 0) *hint = 0xffffffffu;
+        __syncthreads();
+        const uint8_t* xs = a.base + static_cast<int64_t>(s) * a.stripe_stride;
+        uint32_t mask = 0u;
+        for (int64_t u = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x; u < units;
+             u += static_cast<int64_t>(gridDim.x) * 256) {
+            uint32_t in[4 * KG];
+#pragma unroll
+            for (int j = 0; j < 4 * KG; j++) in[j] = j < a.K ? pairs_unit(xs + a.off[j], u, whole, a.len) : 0u;
+            uint32_t nz = 0u;
+            for (int r = 0; r < a.R; r++) {
+                uint32_t acc = 0u;
+                for (int b = 15; b >= 0; b--) {
+                    const uint32_t hi = acc & 0x80008000u;
+                    acc = ((acc & 0x7fff7fffu) << 1) ^ ((hi >> 15) * 0x100bu);
+                    const uint32_t m = a.cmask[r * 16 + b];
+#pragma unroll
+                    for (int j = 0; j < 4 * KG; j++) acc = xor_and(acc, in[j], 0u - ((m >> j) & 1u));
+                }
+                acc ^= pairs_unit(xs + a.off[a.K + r], u, whole, a.len);
+                syn[r * 256] = acc;
+                if (acc != 0u) nz |= 1u << r;
+            }
+            if (nz == 0u) continue;
+            uint32_t got = 0u;
+            for (int c = 0; c < a.singles && got == 0u; c++) {
+                const uint32_t* e = a.table + c * a.stride;
+                if (pairs_single_ok(e, syn, a.R, nz)) got = 1u << (e[0] & 0x1fu);
+            }
+            if (got == 0u) {
+                const uint32_t h = __hip_atomic_load(hint, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                if (h != 0xffffffffu) {
+                    const uint32_t* e = a.table + h * a.stride;
+                    if (pairs_pair_ok(e, syn, a.R)) got = pairs_bits(e[0]);
+                }
+            }
+            for (int i = a.singles; i < a.singles + a.npairs && got == 0u; i++) {
+                const uint32_t* e = a.table + i * a.stride;
+                if (pairs_pair_ok(e, syn, a.R)) {
+                    got = pairs_bits(e[0]);
+                    __hip_atomic_store(hint, static_cast<uint32_t>(i), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                }
+            }
+            mask |= got != 0u ? got : 0xffffffffu;
+        }
+        for (int o = 32; o; o >>= 1) mask |= __shfl_xor(mask, o);
+        if ((threadIdx.x & 63u) == 0u && mask != 0u)
+            __hip_atomic_fetch_or(a.pairs + s, mask, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __syncthreads();  // no lane still stores this stripe's hint when the next one's is reset
+    }
+}
+
+// pairs[s] = the word when it has exactly two bits, else 0 (the last step of ecamd_rs_locate_pairs).
+__global__ void __launch_bounds__(256) pairs_finalize_kernel(uint32_t* pairs, int n)
+{
+    const int s = static_cast<int>(blockIdx.x) * 256 + static_cast<int>(threadIdx.x);
+    if (s < n) {
+        const uint32_t v = pairs[s];
+        pairs[s] = __popc(v) == 2 ? v : 0u;
+    }
+}
+
+std::atomic<long long> g_pairs_launches{0};
+
+// The pair stage of one call, after locate_finalize_kernel on the same stream, which has set d_pairs
+// to 0: with R >= 4 and a table, locate_pairs_kernel and its finalize.  The grid: a chunk per 16 passes
+// of 256 units, at most 64, by as many stripe slots as keep it within 4096 workgroups -- on a clean
+// batch the launch costs what its empty workgroups cost (11 us for 16384 of them, traced); knob
+// pairs_grid > 0 caps both dimensions.
+int locate_pairs(const std::vector<int>& A, int K, int R, const PairsTable& t, const uint8_t* base, int64_t stripe_stride,
+                 const int64_t* in_off, const int64_t* chk_off, int64_t blocksize, int nstripes, const uint32_t* d_status,
+                 const uint32_t* d_suspects, uint32_t* d_pairs, hipStream_t st)
+{
+    if (R < 4 || R > kPairsMaxRows || !t.dev || !t.exact) return 0;
+    PairsArgs a{};
+    a.base = base;
+    a.status = d_status;
+    a.suspects = d_suspects;
+    a.pairs = d_pairs;
+    a.table = t.dev;
+    a.stripe_stride = stripe_stride;
+    a.len = blocksize;
+    for (int j = 0; j < K; j++) a.off[j] = in_off[j];
+    for (int r = 0; r < R; r++) a.off[K + r] = chk_off[r];
+    for (int r = 0; r < R; r++)
+        for (int j = 0; j < K; j++)
+            for (int b = 0; b < 16; b++)
+                if ((A[static_cast<size_t>(r) * K + j] >> b) & 1) a.cmask[r * 16 + b] |= 1u << j;
+    a.nstripes = nstripes;
+    a.K = K;
+    a.R = R;
+    a.singles = t.singles;
+    a.npairs = t.pairs;
+    a.stride = t.stride;
+    const int64_t units = (blocksize + 3) >> 2;
+    int chunks = static_cast<int>(std::clamp<int64_t>((units + 4095) / 4096, 1, 64)), slots = std::min(nstripes, 4096 / chunks);
+    const int cap = dev_tune("pairs_grid");
+    if (cap > 0) {
+        chunks = std::min(chunks, cap);
+        slots = std::min(slots, cap);
+    }
+    const dim3 grid(static_cast<unsigned>(chunks), static_cast<unsigned>(slots)), block(256);
+    const size_t lds = (static_cast<size_t>(R) * 256 + 1) * sizeof(uint32_t);
+    switch ((K + 3) / 4) {  // K <= 28
+    case 1: hipLaunchKernelGGL(locate_pairs_kernel<1>, grid, block, lds, st, a); break;
+    case 2: hipLaunchKernelGGL(locate_pairs_kernel<2>, grid, block, lds, st, a); break;
+    case 3: hipLaunchKernelGGL(locate_pairs_kernel<3>, grid, block, lds, st, a); break;
+    case 4: hipLaunchKernelGGL(locate_pairs_kernel<4>, grid, block, lds, st, a); break;
+    case 5: hipLaunchKernelGGL(locate_pairs_kernel<5>, grid, block, lds, st, a); break;
+    case 6: hipLaunchKernelGGL(locate_pairs_kernel<6>, grid, block, lds, st, a); break;
+    default: hipLaunchKernelGGL(locate_pairs_kernel<7>, grid, block, lds, st, a); break;
+    }
+    HIP_TRY(hipGetLastError());
+    g_pairs_launches.fetch_add(1, std::memory_order_relaxed);
+    hipLaunchKernelGGL(pairs_finalize_kernel, dim3(static_cast<unsigned>((nstripes + 255) / 256)), dim3(256), 0, st, d_pairs,
+                       nstripes);
+    HIP_TRY(hipGetLastError());
+    return 0;
 }
 
 // ---- flat XOR, fused stage: xor_check_kernel -------------------------------------------------
@@ -373,6 +587,7 @@ struct CheckPlan {
     std::vector<uint32_t> masks;     // flat XOR: ecamd_xor_apply_strided over the parity bitmaps; whole tiles take
     std::vector<uint32_t> sig;       //   xor_check_fused with the signatures of ecamd_xor_check_plan
     CheckMap cached;                 // what A and map point into: the cached check map (rs_vand)
+    PairsTable pairs;                //   and its pair table (ecamd_rs_locate_pairs)
     std::vector<int> bitmaps;        // or the parity bitmaps as 0 / 1 (flat XOR)
 };
 
@@ -482,10 +697,11 @@ void locate_tables(const std::vector<int>& A, int R, int K, LocateCmpArgs& l)
 }
 
 // The check (d_suspects null) or locate of one validated call: both arrays set, the fused stage over
-// whole tiles, the generic stage over the rest, the finalize step of a locate.  StreamUse: the scratch
-// of the stream context outlives the call.
+// whole tiles, the generic stage over the rest, the finalize step of a locate and, with d_pairs, the
+// pair stage on its results.  StreamUse: the scratch of the stream context outlives the call.
 int run_check(int dev, const CheckPlan& p, const void* base, int64_t stripe_stride, int64_t frag_stride,
-              int64_t blocksize, int nstripes, uint32_t* d_status, uint32_t* d_suspects, void* stream)
+              int64_t blocksize, int nstripes, uint32_t* d_status, uint32_t* d_suspects, void* stream,
+              uint32_t* d_pairs = nullptr)
 {
     if (nstripes == 0) return 0;
     const StreamUse use(dev, stream);
@@ -542,15 +758,18 @@ int run_check(int dev, const CheckPlan& p, const void* base, int64_t stripe_stri
                                  blocksize, nstripes, d_status, locating ? &loc : nullptr);
     if (rc || !d_suspects) return rc;
     hipLaunchKernelGGL(locate_finalize_kernel, dim3(static_cast<unsigned>((nstripes + 255) / 256)), dim3(256), 0, st,
-                       d_status, d_suspects, participating, nstripes);
+                       d_status, d_suspects, participating, nstripes, d_pairs);
     HIP_TRY(hipGetLastError());
-    return 0;
+    if (!d_pairs || R < 4) return 0;  // fewer than four checks leave d_pairs zero
+    return locate_pairs(*p.A, K, R, p.pairs, b, stripe_stride, in_off.data(), chk_off.data(), blocksize, nstripes, d_status,
+                        d_suspects, d_pairs, st);
 }
 
-// ecamd_rs_check (locate false) and ecamd_rs_locate: a bad layout is reported before too many missing
-// fragments, so it is checked before the plan is made.
+// ecamd_rs_check (locate false), ecamd_rs_locate and ecamd_rs_locate_pairs (pairs true): a bad layout
+// is reported before too many missing fragments, so it is checked before the plan is made.
 int rs_call(bool locate, int k, int m, const int* missing, const void* base, int64_t stripe_stride, int64_t frag_stride,
-            int64_t blocksize, int nstripes, uint32_t* d_status, uint32_t* d_suspects, uint32_t* checked, void* stream)
+            int64_t blocksize, int nstripes, uint32_t* d_status, uint32_t* d_suspects, uint32_t* checked, void* stream,
+            bool pairs = false, uint32_t* d_pairs = nullptr)
 {
     int dev = 0;
     int rc = dev_ensure(&dev);
@@ -558,8 +777,10 @@ int rs_call(bool locate, int k, int m, const int* missing, const void* base, int
     if (k <= 0 || m < 0 || k + m > 32)
         return dev_fail(ECAMD_EINVAL, "%s needs k + m <= 32 (k=%d m=%d)", locate ? "locate" : "check", k, m);
     if ((rc = check_layout(locate, base, stripe_stride, frag_stride, blocksize, nstripes, d_status, d_suspects))) return rc;
+    if (pairs && !d_pairs) return dev_fail(ECAMD_EINVAL, "null pairs");
     CheckPlan p;
     if ((rc = check_map(k, m, missing, p.cached))) return rc;
+    if (pairs && (rc = check_map_pairs(p.cached, p.pairs))) return rc;
     p.inputs = *p.cached.inputs;
     p.checked = *p.cached.checked;
     p.A = p.cached.coeff;
@@ -568,7 +789,7 @@ int rs_call(bool locate, int k, int m, const int* missing, const void* base, int
     for (int f : p.checked) mask |= 1u << f;
     if (checked) *checked = mask;  // for an empty batch too
     return run_check(dev, p, base, stripe_stride, frag_stride, blocksize, nstripes, d_status, locate ? d_suspects : nullptr,
-                     stream);
+                     stream, pairs ? d_pairs : nullptr);
 }
 
 // ecamd_xor_check (locate false) and ecamd_xor_locate: the parity bitmaps as a 0 / 1 map over GF(2^16).
@@ -596,31 +817,45 @@ int xor_call(bool locate, int k, int m, int hd, const void* base, int64_t stripe
                      stream);
 }
 
-// The host half of ecamd_rs_scrub and ecamd_xor_scrub, after the locate: a wait for `stream`, both
-// arrays read back, the counts, and -- when a stripe has exactly one suspect -- decode(lists) with
-// lists[2*s..] = {f, -1} for such a stripe and {-1, -1} (the empty list) for every other.
+// The host half of ecamd_rs_scrub, ecamd_xor_scrub and ecamd_rs_scrub_pairs, after the locate: a wait
+// for `stream`, the arrays read back, the counts, and -- when a stripe has exactly one suspect --
+// decode(lists) with lists[2*s..] = {f, -1} for such a stripe and {-1, -1} (the empty list) for every
+// other.  With d_pairs the lists are 3 long: {f, -1, -1}, {a, b, -1} for a stripe with a pair, and
+// the empty list.
 template <class Decode>
 int scrub_located(const uint32_t* d_status, const uint32_t* d_suspects, int nstripes, int* n_clean, int* n_repaired,
-                  int* n_unlocated, void* stream, Decode&& decode)
+                  int* n_unlocated, void* stream, Decode&& decode, const uint32_t* d_pairs = nullptr,
+                  int* n_repaired_pairs = nullptr)
 {
-    int clean = 0, repaired = 0, unlocated = 0;
+    int clean = 0, repaired = 0, unlocated = 0, repaired_pairs = 0;
+    const size_t width = d_pairs ? 3 : 2;
     if (nstripes > 0) {
         HIP_TRY(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
         std::vector<uint32_t> status(static_cast<size_t>(nstripes)), suspects(static_cast<size_t>(nstripes));
         HIP_TRY(hipMemcpy(status.data(), d_status, status.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
         HIP_TRY(hipMemcpy(suspects.data(), d_suspects, suspects.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        std::vector<int> lists(static_cast<size_t>(nstripes) * 2, -1);
+        std::vector<uint32_t> pairs;
+        if (d_pairs) {
+            pairs.resize(static_cast<size_t>(nstripes));
+            HIP_TRY(hipMemcpy(pairs.data(), d_pairs, pairs.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        }
+        std::vector<int> lists(static_cast<size_t>(nstripes) * width, -1);
         for (int s = 0; s < nstripes; s++) {
             const uint32_t sus = suspects[static_cast<size_t>(s)];
+            const uint32_t pr = d_pairs ? pairs[static_cast<size_t>(s)] : 0u;
             if (!status[static_cast<size_t>(s)])
                 clean++;
             else if (sus && !(sus & (sus - 1))) {
-                lists[static_cast<size_t>(s) * 2] = __builtin_ctz(sus);
+                lists[static_cast<size_t>(s) * width] = __builtin_ctz(sus);
                 repaired++;
+            } else if (!sus && __builtin_popcount(pr) == 2) {
+                lists[static_cast<size_t>(s) * width] = __builtin_ctz(pr);
+                lists[static_cast<size_t>(s) * width + 1] = 31 - __builtin_clz(pr);
+                repaired_pairs++;
             } else
                 unlocated++;
         }
-        if (repaired) {
+        if (repaired || repaired_pairs) {
             const int rc = decode(lists.data());
             if (rc) return rc;
         }
@@ -628,6 +863,7 @@ int scrub_located(const uint32_t* d_status, const uint32_t* d_suspects, int nstr
     if (n_clean) *n_clean = clean;
     if (n_repaired) *n_repaired = repaired;
     if (n_unlocated) *n_unlocated = unlocated;
+    if (n_repaired_pairs) *n_repaired_pairs = repaired_pairs;
     return 0;
 }
 
@@ -704,6 +940,32 @@ int ecamd_rs_scrub(int k, int m, void* base, int64_t stripe_stride, int64_t frag
         return ecamd_rs_decode_multi(k, m, lists, 2, 1, base, stripe_stride, frag_stride, blocksize, nstripes, stream);
     });
 }
+
+int ecamd_rs_locate_pairs(int k, int m, const int* missing, const void* base, int64_t stripe_stride, int64_t frag_stride,
+                          int64_t blocksize, int nstripes, uint32_t* d_status, uint32_t* d_suspects, uint32_t* d_pairs,
+                          uint32_t* checked, void* stream)
+{
+    return rs_call(true, k, m, missing, base, stripe_stride, frag_stride, blocksize, nstripes, d_status, d_suspects, checked,
+                   stream, true, d_pairs);
+}
+
+int ecamd_rs_scrub_pairs(int k, int m, void* base, int64_t stripe_stride, int64_t frag_stride, int64_t blocksize,
+                         int nstripes, uint32_t* d_status, uint32_t* d_suspects, uint32_t* d_pairs, int* n_clean,
+                         int* n_repaired, int* n_repaired_pairs, int* n_unlocated, void* stream)
+{
+    if (m < 4) return dev_fail(ECAMD_EINVAL, "a pair repair needs m >= 4 (m=%d)", m);
+    int rc = ecamd_rs_locate_pairs(k, m, nullptr, base, stripe_stride, frag_stride, blocksize, nstripes, d_status, d_suspects,
+                                   d_pairs, nullptr, stream);
+    if (rc) return rc;
+    return scrub_located(
+        d_status, d_suspects, nstripes, n_clean, n_repaired, n_unlocated, stream,
+        [&](const int* lists) {
+            return ecamd_rs_decode_multi(k, m, lists, 3, 1, base, stripe_stride, frag_stride, blocksize, nstripes, stream);
+        },
+        d_pairs, n_repaired_pairs);
+}
+
+long long ecamd_locate_pairs_launches(void) { return g_pairs_launches.load(std::memory_order_relaxed); }
 
 int ecamd_xor_scrub(int k, int m, int hd, void* base, int64_t stripe_stride, int64_t frag_stride, int64_t blocksize,
                     int nstripes, uint32_t* d_status, uint32_t* d_suspects, int* n_clean, int* n_repaired,

@@ -365,6 +365,8 @@ struct Tuning {
     Knob xor_check_threads{0};    // xor_check_kernel: 64 / 256 threads per workgroup = 1 / 4 KiB tiles; 0 = the
                                   //   default, 64 at every size (measured: xor_check_fused in ecamd_check.hip,
                                   //   DESIGN.md "Flat XOR: fused check, locate and scrub")
+    Knob pairs_grid{0};           // locate_pairs_kernel (ecamd_check.hip): > 0 caps both grid dimensions (chunks
+                                  //   per stripe, stripe slots), so tests make both grid-stride loops iterate
     Knob bs_wave{1};              // ecamd_bs_kernel in one-wave workgroups of 4 KiB tiles (64 lanes x 4
                                   //   chunks 1 KiB apart, built with a 2-wave register budget) instead of
                                   //   4-wave 16 KiB tiles: 1 (default) row groups of bs_wave_min_rows..4
@@ -467,6 +469,7 @@ int dev_tune(const char* key)
     const std::string k(key);
     if (k == "xor_check_fused") return g_tune.xor_check_fused;
     if (k == "xor_check_threads") return g_tune.xor_check_threads;
+    if (k == "pairs_grid") return g_tune.pairs_grid;
     if (k == "xor_tiles_per_slot") return g_tune.xor_tiles_per_slot;
     if (k == "xor_wgs") return g_tune.xor_wgs;
     if (k == "crc_bits") return g_tune.crc_bits;
@@ -1826,6 +1829,15 @@ int launch_xor(const uint32_t* masks, int R, int K, ApplyArgs base_args, const i
 struct RsEntry {
     std::unique_ptr<ecamd_map, void (*)(ecamd_map*)> map{nullptr, ecamd_map_destroy};
     std::vector<int> inputs, outputs;
+    // check maps only (kind 4): the pair table of check_map_pairs, made once on demand
+    std::once_flag pairs_once;
+    PairsTable pairs;
+    int pairs_rc = 0;
+    void* pairs_dev = nullptr;
+    ~RsEntry()
+    {
+        if (pairs_dev) (void)hipFree(pairs_dev);
+    }
 };
 
 // Bounded LRU of prepared maps keyed by (device, kind, k, m, rebuild, dest, erasures): a long-lived
@@ -1955,6 +1967,65 @@ int check_map(int k, int m, const int* missing, CheckMap& out)
     out.map = e->map.get();
     out.coeff = e->map ? &e->map->coeff : nullptr;
     out.hold = e;
+    return 0;
+}
+
+int check_map_pairs(const CheckMap& cm, PairsTable& out)
+{
+    out = PairsTable();
+    auto* e = const_cast<RsEntry*>(static_cast<const RsEntry*>(cm.hold.get()));
+    if (!e || !cm.coeff) return 0;
+    std::call_once(e->pairs_once, [e, &cm] {
+        const int K = static_cast<int>(e->inputs.size()), R = static_cast<int>(e->outputs.size());
+        const PairPlan plan = rs_locate_pairs_plan(*cm.coeff, R, K);
+        if (!plan.pairs || !plan.independent4) return;  // no table: d_pairs stays zero
+        const GF16& gf = GF16::get();
+        const int P = K + R, stride = 2 + R;
+        auto frag = [&](int c) { return static_cast<uint32_t>(c < K ? e->inputs[c] : e->outputs[c - K]); };
+        std::vector<uint32_t> tab;
+        for (int c = 0; c < P; c++) {  // the single participants
+            std::vector<int> col(static_cast<size_t>(R));
+            int p = -1;
+            uint32_t rows = 0;
+            for (int r = 0; r < R; r++) {
+                col[r] = c < K ? (*cm.coeff)[static_cast<size_t>(r) * K + c] : (r == c - K);
+                if (col[r]) {
+                    if (p < 0) p = r;
+                    rows |= 1u << r;
+                }
+            }
+            // (an all-zero column cannot be independent of the others)
+            tab.push_back(frag(c) | 0xffu << 8 | static_cast<uint32_t>(std::max(p, 0)) << 16 | 0xffu << 24);
+            tab.push_back(rows);
+            for (int r = 0; r < R; r++) tab.push_back(p < 0 ? 0u : static_cast<uint32_t>(gf.mul(col[r], gf.inv(col[p]))));
+        }
+        int npairs = 0, i = 0;
+        for (int a = 0; a < P; a++)
+            for (int b = a + 1; b < P; b++, i++) {
+                const int p = plan.pivot[static_cast<size_t>(i) * 2], q = plan.pivot[static_cast<size_t>(i) * 2 + 1];
+                if (p < 0) continue;
+                tab.push_back(frag(a) | frag(b) << 8 | static_cast<uint32_t>(p) << 16 | static_cast<uint32_t>(q) << 24);
+                tab.push_back(0u);
+                for (int r = 0; r < R; r++) {
+                    const int* l = &plan.L[(static_cast<size_t>(i) * R + r) * 2];
+                    tab.push_back(static_cast<uint32_t>(l[0]) | static_cast<uint32_t>(l[1]) << 16);
+                }
+                npairs++;
+            }
+        hipError_t err = hipMalloc(&e->pairs_dev, tab.size() * sizeof(uint32_t));
+        if (err == hipSuccess) err = hipMemcpy(e->pairs_dev, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+        if (err != hipSuccess) {
+            e->pairs_rc = fail(ECAMD_EHIP, "pair table: %s", hipGetErrorString(err));
+            return;
+        }
+        e->pairs.dev = static_cast<const uint32_t*>(e->pairs_dev);
+        e->pairs.singles = P;
+        e->pairs.pairs = npairs;
+        e->pairs.stride = stride;
+        e->pairs.exact = true;
+    });
+    if (e->pairs_rc) return fail(ECAMD_EHIP, "pair table upload failed");
+    out = e->pairs;
     return 0;
 }
 
@@ -2971,6 +3042,8 @@ int ecamd_tune(const char* key, int value)
         g_tune.xor_check_fused = value != 0;  // < 0: the default (1)
     } else if (k == "xor_check_threads") {
         g_tune.xor_check_threads = value == 64 || value == 256 ? value : 0;  // else the default (64)
+    } else if (k == "pairs_grid") {
+        g_tune.pairs_grid = std::max(0, std::min(value, 65535));  // <= 0: the default (by shape)
     } else if (k == "xor_grid") {
         g_tune.xor_grid = value != 0;  // < 0: the default (1)
     } else if (k == "bs_wave") {

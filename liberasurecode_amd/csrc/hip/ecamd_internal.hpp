@@ -96,6 +96,21 @@ struct CheckMap {
     std::shared_ptr<const void> hold;
 };
 int check_map(int k, int m, const int* missing, CheckMap& out);
+// The pair plan of a cached check map (rs_locate_pairs_plan, host/gf16.hpp) as the device table
+// locate_pairs_kernel reads, made at the first call that asks for it and kept with the map.  Entries
+// of 2 + R words: [0] fragment a | fragment b << 8 | pivot row p << 16 | pivot row q << 24, [1] the
+// rows a single participant must leave non-zero -- exactly those --, [2 + r] L[r][0] | L[r][1] << 16.
+// First the K + R single participants (b and q 0xff; L[r][0] = column[r] / column[p], p its first
+// non-zero row), then the pairs that can be tested (dependent ones left out).  `exact`: any four
+// columns of [A | I] are independent, so the pair is unique; dev is null when it is not, or when
+// R < 4 (the call then leaves d_pairs zero).  The table is at most 18 KiB and is freed with its entry;
+// it is not counted against the map cache's byte limit.
+struct PairsTable {
+    const uint32_t* dev = nullptr;
+    int singles = 0, pairs = 0, stride = 0;
+    bool exact = false;
+};
+int check_map_pairs(const CheckMap& cm, PairsTable& out);
 // Fused stage of a check or, with d_suspects, of a locate: rows [row0, row0 + nrows) of the R x K
 // matrix A as the syndrome map [A | I] through the check / locate form of the bitsliced kernel, over
 // whole tiles of every stripe.  Input j of stripe s at base + s*stripe_stride + in_off[j], fragment

@@ -285,4 +285,71 @@ int rs_locate_map(const std::vector<int>& G, int k, int m, const std::vector<int
     return 0;
 }
 
+PairPlan rs_locate_pairs_plan(const std::vector<int>& coeff, int R, int K)
+{
+    PairPlan out;
+    out.K = K;
+    out.R = R;
+    if (R < 4 || K <= 0 || coeff.size() != static_cast<size_t>(R) * K) return out;
+    const GF16& gf = GF16::get();
+    const int P = K + R;
+    std::vector<int> col(static_cast<size_t>(P) * R, 0);  // column c of [A | I] at col[c*R..]
+    for (int c = 0; c < P; c++)
+        for (int r = 0; r < R; r++)
+            col[static_cast<size_t>(c) * R + r] = c < K ? coeff[static_cast<size_t>(r) * K + c] : (r == c - K);
+    out.pairs = P * (P - 1) / 2;
+    out.pivot.assign(static_cast<size_t>(out.pairs) * 2, -1);
+    out.L.assign(static_cast<size_t>(out.pairs) * R * 2, 0);
+    int i = 0;
+    for (int a = 0; a < P; a++)
+        for (int b = a + 1; b < P; b++, i++) {
+            const int* ca = &col[static_cast<size_t>(a) * R];
+            const int* cb = &col[static_cast<size_t>(b) * R];
+            int det = 0, p = 0, q = 0;
+            for (p = 0; p < R && !det; p++)
+                for (q = p + 1; q < R && !det; q++) det = gf.mul(ca[p], cb[q]) ^ gf.mul(ca[q], cb[p]);
+            if (!det) continue;  // dependent columns: never
+            p--;
+            q--;
+            out.pivot[static_cast<size_t>(i) * 2] = p;
+            out.pivot[static_cast<size_t>(i) * 2 + 1] = q;
+            // (S_p, S_q) = M (x, y) with M = [ca_p cb_p; ca_q cb_q]; S_r = (ca_r, cb_r) inv(M) (S_p, S_q)
+            const int di = gf.inv(det);
+            for (int r = 0; r < R; r++) {
+                int* l = &out.L[(static_cast<size_t>(i) * R + r) * 2];
+                l[0] = gf.mul(gf.mul(ca[r], cb[q]) ^ gf.mul(cb[r], ca[q]), di);
+                l[1] = gf.mul(gf.mul(ca[r], cb[p]) ^ gf.mul(cb[r], ca[p]), di);
+            }
+        }
+    // any four columns independent: eliminate each 4-subset's R x 4 matrix column by column
+    out.independent4 = true;
+    int sel[4];
+    for (sel[0] = 0; sel[0] < P && out.independent4; sel[0]++)
+        for (sel[1] = sel[0] + 1; sel[1] < P && out.independent4; sel[1]++)
+            for (sel[2] = sel[1] + 1; sel[2] < P && out.independent4; sel[2]++)
+                for (sel[3] = sel[2] + 1; sel[3] < P && out.independent4; sel[3]++) {
+                    int v[4][32];
+                    for (int c = 0; c < 4; c++)
+                        for (int r = 0; r < R; r++) v[c][r] = col[static_cast<size_t>(sel[c]) * R + r];
+                    bool used[32] = {false};
+                    for (int c = 0; c < 4 && out.independent4; c++) {
+                        int pr = -1;
+                        for (int r = 0; r < R && pr < 0; r++)
+                            if (!used[r] && v[c][r]) pr = r;
+                        if (pr < 0) {
+                            out.independent4 = false;
+                            break;
+                        }
+                        used[pr] = true;
+                        const int inv = gf.inv(v[c][pr]);
+                        for (int d = c + 1; d < 4; d++) {
+                            const int f = gf.mul(v[d][pr], inv);
+                            if (!f) continue;
+                            for (int r = 0; r < R; r++) v[d][r] ^= gf.mul(f, v[c][r]);
+                        }
+                    }
+                }
+    return out;
+}
+
 }  // namespace ecamd

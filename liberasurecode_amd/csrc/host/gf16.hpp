@@ -73,6 +73,23 @@ int rs_check_map(const std::vector<int>& G, int k, int m, const std::vector<int>
 int rs_locate_map(const std::vector<int>& G, int k, int m, const std::vector<int>& missing,
                   FragmentMap& out, std::vector<int>& ratio);
 
+// Pair plan (ecamd_rs_locate_pairs): which TWO participants of a check map explain a syndrome.  The
+// participants are the K inputs (0..K-1), then the R checked rows (K..K+R-1); participant c has column
+// c of the R x (K+R) syndrome matrix [A | I].  Pair i of a < b, in the order (0,1), (0,2), ...,
+// (K+R-2, K+R-1): pivot[2i..] = two rows (p, q) whose 2 x 2 minor of columns a, b is non-singular, and
+// L[(i*R + r)*2..] with S_r == L[r][0]*S_p ^ L[r][1]*S_q for every row r exactly when the syndrome S lies
+// in the span of the two columns (rows p and q of L are (1,0) and (0,1)).  A pair of dependent columns
+// has pivot (-1, -1) and zero L rows: it is never tested.  independent4: any four columns of [A | I] are
+// linearly independent, so a syndrome that needs two columns lies in the span of no other pair (at
+// most C(K+R, 4) rank computations).  Empty (pairs 0) for R < 4.
+struct PairPlan {
+    int K = 0, R = 0, pairs = 0;
+    bool independent4 = false;
+    std::vector<int> pivot;  // pairs x 2
+    std::vector<int> L;      // pairs x R x 2
+};
+PairPlan rs_locate_pairs_plan(const std::vector<int>& coeff, int R, int K);
+
 // Encode map: inputs 0..k-1, outputs k..k+m-1, generator parity rows.
 FragmentMap rs_encode_map(const std::vector<int>& G, int k, int m);
 

@@ -116,6 +116,32 @@ int ecamd_rs_locate_map(const int* G, int k, int m, const int* missing, int* inp
     return 0;
 }
 
+int ecamd_rs_locate_pairs_map(const int* G, int k, int m, const int* missing, int* inputs, int* checked,
+                              int* coeff, int* ncheck, int* npairs, int* pivots, int* L, int* independent4)
+{
+    if (!G || k <= 0 || m < 0 || !inputs || !ncheck || !npairs || !independent4) return -1;
+    std::vector<int> g(G, G + static_cast<size_t>(k + m) * k);
+    FragmentMap fm;
+    if (rs_check_map(g, k, m, minus1_list(missing), fm) != 0) return -1;
+    std::memcpy(inputs, fm.inputs.data(), fm.inputs.size() * sizeof(int));
+    if (!fm.outputs.empty()) {
+        if (!checked || !coeff) return -1;
+        std::memcpy(checked, fm.outputs.data(), fm.outputs.size() * sizeof(int));
+        std::memcpy(coeff, fm.coeff.data(), fm.coeff.size() * sizeof(int));
+    }
+    const int R = static_cast<int>(fm.outputs.size());
+    const PairPlan plan = rs_locate_pairs_plan(fm.coeff, R, k);
+    if (plan.pairs) {
+        if (!pivots || !L) return -1;
+        std::memcpy(pivots, plan.pivot.data(), plan.pivot.size() * sizeof(int));
+        std::memcpy(L, plan.L.data(), plan.L.size() * sizeof(int));
+    }
+    *ncheck = R;
+    *npairs = plan.pairs;
+    *independent4 = plan.independent4 ? 1 : 0;
+    return 0;
+}
+
 int ecamd_split_tables(const int* coeff, int R, int K, int row0, int width, int col0, int ncols,
                        uint8_t* out)
 {

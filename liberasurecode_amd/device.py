@@ -229,6 +229,47 @@ def rs_scrub(k, m, lay: Layout, stream=None):
     return status, suspects, tuple(c.value for c in counts)
 
 
+def _status_suspects_pairs(call, lay, stream, what):
+    """Run call(d_status, d_suspects, d_pairs) and return the three arrays of nstripes words (waits
+    for `stream`)."""
+    n = max(lay.nstripes, 1)
+    buf = DeviceBuffer(12 * n)
+    try:
+        check(call(buf.ptr, buf.ptr + 4 * n, buf.ptr + 8 * n), what)
+        if stream is not None:
+            stream.synchronize()
+        words = buf.download(12 * n).view(np.uint32)
+        return tuple(words[i * n:i * n + lay.nstripes].copy() for i in range(3))
+    finally:
+        buf.free()
+
+
+def rs_locate_pairs(k, m, lay: Layout, missing=(), stream=None):
+    """ecamd_rs_locate_pairs: (status, suspects, pairs, checked_mask).  status, suspects and the mask
+    as rs_locate; pairs[s] has exactly the two bits {a, b} when stripe s is dirty, has no suspect, at
+    least 4 fragments were checked and {a, b} is the one pair of fragments that explains every dirty
+    word, else 0."""
+    checked = C.c_uint32(0)
+    status, suspects, pairs = _status_suspects_pairs(lambda d, u, p: dev().ecamd_rs_locate_pairs(
+        k, m, ints(list(missing) + [-1]), lay.buf.ptr, lay.stripe_stride, lay.frag_stride, lay.blocksize,
+        lay.nstripes, d, u, p, C.byref(checked), _s(stream)), lay, stream, "rs_locate_pairs")
+    return status, suspects, pairs, checked.value
+
+
+def rs_scrub_pairs(k, m, lay: Layout, stream=None):
+    """ecamd_rs_scrub_pairs on full stripes (m >= 4): locate, then repair in place every stripe with
+    exactly one suspect and every stripe with a pair.  Returns (status, suspects, pairs, (n_clean,
+    n_repaired, n_repaired_pairs, n_unlocated)); waits for `stream`, so the repairs are complete on
+    return."""
+    counts = [C.c_int(0) for _ in range(4)]
+    status, suspects, pairs = _status_suspects_pairs(lambda d, u, p: dev().ecamd_rs_scrub_pairs(
+        k, m, lay.buf.ptr, lay.stripe_stride, lay.frag_stride, lay.blocksize, lay.nstripes, d, u, p,
+        *[C.byref(c) for c in counts], _s(stream)), lay, stream, "rs_scrub_pairs")
+    if stream is None:
+        check(dev().ecamd_synchronize(), "synchronize")
+    return status, suspects, pairs, tuple(c.value for c in counts)
+
+
 def xor_scrub(k, m, hd, lay: Layout, stream=None):
     """ecamd_xor_scrub on full flat_xor_hd stripes: locate, then repair in place every stripe with
     exactly one suspect.  Returns (status, suspects, (n_clean, n_repaired, n_unlocated)) as rs_scrub;

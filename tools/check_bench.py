@@ -24,7 +24,14 @@ kernel existed) and (c) each tile form of the fused kernel (knob xor_check_threa
 default), on clean data and then on an all-dirty batch (data fragment 1 of every stripe rewritten).
 The bar for (c) on clean data is (a)'s mean plus the spread of (a)'s own repetitions.  `--tree DIR` runs
 the tool against the package and built libraries of another checkout: with the parent commit's, `--xor`
-gives (a) and (b) as that commit runs them (it has the generic path alone)."""
+gives (a) and (b) as that commit runs them (it has the generic path alone).
+
+`--pairs` measures ecamd_rs_locate_pairs (C3 only) against ecamd_rs_locate, alternating: (a) on a clean
+batch -- the pair stage adds one memset, one launch whose workgroups all end after two loads, and one
+finalize --, (b) with one stripe of 256 holding two damaged words, (c) with two fragments of every
+stripe rewritten, so that every word needs the pair.  With `--tree DIR` of the parent commit it times
+ecamd_rs_locate alone (`--locate-only`: the same on this commit); `--pairs-merge THIS,BEFORE,AFTER` joins this commit's document with two such
+runs of the same session, before and after it: their spread is the margin for (a)."""
 import argparse
 import json
 import os
@@ -183,6 +190,80 @@ def run_locate(d, st, reps, n):
     return out
 
 
+def run_pairs(d, st, reps, n, locate_only=False):
+    """C3, ecamd_rs_locate against ecamd_rs_locate_pairs, alternating: (a) a clean batch, (b) one stripe
+    of 256 with two damaged words, (c) fragments 3 and 12 of every stripe rewritten.  A tree from before
+    the pair stage (--tree) has ecamd_rs_locate alone: its rows are the yardstick of (a)."""
+    k, m, F, S = 10, 4, 1 << 20, 256
+    has_pairs = hasattr(d, "ecamd_rs_locate_pairs") and not locate_only
+    lay = D.Layout.alloc(k + m, F, S)
+    words = D.DeviceBuffer(12 * S)
+    checked = _lib.u32s([0])
+    args = (lay.buf.ptr, lay.stripe_stride, lay.frag_stride, F, S)
+
+    def locate():
+        _lib.check(d.ecamd_rs_locate(k, m, None, *args, words.ptr, words.ptr + 4 * S, checked, st.handle), "rs_locate")
+
+    def pairs():
+        _lib.check(d.ecamd_rs_locate_pairs(k, m, None, *args, words.ptr, words.ptr + 4 * S, words.ptr + 8 * S, checked,
+                                           st.handle), "rs_locate_pairs")
+
+    def fresh():
+        lay.fill_splitmix(nfrags=k, stream=st)
+        D.rs_encode(k, m, lay, stream=st)
+
+    def result():
+        (pairs if has_pairs else locate)()
+        st.synchronize()
+        got = words.download().view("uint32")
+        return got[:S], got[S:2 * S], got[2 * S:]
+
+    def rounds(ms, suffix):
+        for _ in range(reps):
+            ms["locate_" + suffix].append(timed(st, locate, n))
+            if has_pairs:
+                ms["pairs_" + suffix].append(timed(st, pairs, n))
+
+    d.ecamd_tune(b"bitslice", 2)
+    fresh()
+    status, suspects, prs = result()
+    assert not status.any() and not suspects.any() and (not has_pairs or not prs.any()), "encoded stripes must read clean"
+    for _ in range(60):  # settle the clocks
+        locate()
+    st.synchronize()
+    algo = S * (k + m) * F
+    ms = {"%s_%s" % (op, case): [] for op in ("locate", "pairs") for case in ("clean", "one_dirty", "all_dirty")}
+    rounds(ms, "clean")
+    # (b) stripe 77: one word of fragment 2 and one of fragment 11
+    for f, at in ((2, 123456), (11, 987654)):
+        pos = 77 * lay.stripe_stride + f * lay.frag_stride + at
+        two = lay.buf.download(2, pos)
+        two[0] ^= 0x5A
+        two[1] ^= 0x01
+        lay.buf.upload(two, pos)
+    status, suspects, prs = result()
+    assert status[77] and not suspects.any() and sum(1 for x in status if x) == 1
+    assert not has_pairs or (prs[77] == (1 << 2 | 1 << 11) and sum(1 for x in prs if x) == 1), "stripe 77 must name {2, 11}"
+    rounds(ms, "one_dirty")
+    # (c) fragments 3 and 12 of every stripe hold other data, so every word of every stripe needs the pair
+    fresh()
+    for f, seed in ((3, 0x5EED), (12, 0xBEEF)):
+        _lib.check(d.ecamd_fill_splitmix(lay.buf.ptr + f * lay.frag_stride, lay.stripe_stride, lay.frag_stride, 1, F, S, 0,
+                                         seed, st.handle), "fill")
+    status, suspects, prs = result()
+    assert status.all() and not suspects.any()
+    assert not has_pairs or (prs == (1 << 3 | 1 << 12)).all(), "every stripe must name {3, 12}"
+    rounds(ms, "all_dirty")
+    out = {"k": k, "m": m, "fragment_bytes": F, "stripes": S, "algorithmic_bytes": algo, "pair_stage": has_pairs}
+    out.update({name: series(v, algo) for name, v in ms.items() if v})
+    if has_pairs:
+        out["clean_pairs_minus_locate_ms"] = round(out["pairs_clean"]["mean_ms"] - out["locate_clean"]["mean_ms"], 4)
+        out["all_dirty_pairs_over_locate"] = round(out["pairs_all_dirty"]["mean_ms"] / out["locate_all_dirty"]["mean_ms"], 3)
+    lay.buf.free()
+    words.free()
+    return out
+
+
 XOR_FORMS = (("generic", 0, 0), ("fused_4k", 1, 256), ("fused_1k", 1, 64), ("fused_default", 1, 0))
 
 
@@ -272,6 +353,10 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--locate", action="store_true", help="measure ecamd_rs_locate at C3 instead")
     ap.add_argument("--xor", action="store_true", help="measure ecamd_xor_check / ecamd_xor_locate instead")
+    ap.add_argument("--pairs", action="store_true", help="measure ecamd_rs_locate_pairs at C3 instead")
+    ap.add_argument("--locate-only", action="store_true", help="with --pairs: time ecamd_rs_locate alone, as --tree PARENT does")
+    ap.add_argument("--pairs-merge", default=None,
+                    help="THIS,BEFORE,AFTER: --pairs documents of this commit and of two runs of the parent's tree")
     ap.add_argument("--xor-shapes", default="10,6,4,1048576,256;3,3,3,4096,131072",
                     help="k,m,hd,fragment bytes,stripes; ...")
     ap.add_argument("--tree", default=None, help="run against the package and libraries of another built checkout")
@@ -284,6 +369,25 @@ def main():
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     assert a.reps >= 5, "at least 5 alternating repetitions"
+    if a.pairs_merge:
+        # this commit's --pairs document with the yardstick of (a): the parent commit's clean
+        # ecamd_rs_locate of the same session, run before and after it (--pairs --tree PARENT)
+        docs = []
+        for path in a.pairs_merge.split(","):
+            with open(path) as f:
+                docs.append(json.load(f))
+        doc, before, after = docs
+        b, c = before["c3"]["locate_clean"]["mean_ms"], after["c3"]["locate_clean"]["mean_ms"]
+        mean = doc["c3"]["pairs_clean"]["mean_ms"]
+        doc["yardstick"] = {"parent_locate_clean_ms": [b, c], "margin_ms": round(abs(b - c), 4), "pairs_clean_mean_ms": mean,
+                            "within": bool(mean <= max(b, c) + abs(b - c)),
+                            "parent_before": before["c3"], "parent_after": after["c3"]}
+        text = json.dumps(doc, indent=1)
+        print(text)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write(text + "\n")
+        return
     d = _lib.dev()
     st = D.Stream()
     per_cu = [int(x) for x in a.per_cu.split(",") if x.strip()]
@@ -292,6 +396,16 @@ def main():
         for shape in a.xor_shapes.split(";"):
             k, m, hd, F, S = (int(x) for x in shape.split(","))
             doc["shapes"].append(run_xor(d, st, k, m, hd, F, S, a.reps, a.n))
+        text = json.dumps(doc, indent=1)
+        print(text)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write(text + "\n")
+        return
+    if a.pairs:
+        doc = {"tool": "tools/check_bench.py --pairs", "reps": a.reps, "calls_per_rep": a.n,
+               "c3": run_pairs(d, st, a.reps, a.n, a.locate_only)}
+        d.ecamd_tune(b"bitslice", 1)
         text = json.dumps(doc, indent=1)
         print(text)
         if a.out:
