@@ -41,7 +41,8 @@ const char *ecamd_last_error(void);
 /* Launch-geometry knobs for sweeps ("threads", "wgs_per_cu", "nt", "grid_mult", "tiles_per_slot",
  * "xor_tiles_per_slot", "bs_tiles_per_slot", "scatter_lanes", ...; every setting produces
  * bit-identical results, only the launch shape changes); 0 restores the default (for
- * xor_ / bs_tiles_per_slot 0 means one launch per pass, a negative value the default).  Safe to
+ * xor_ / bs_tiles_per_slot 0 means one launch per pass, a negative value the default).  The list
+ * of knobs, with each one's default and rule: csrc/host/tune.hpp (tune_knobs.def).  Safe to
  * call while other threads launch: each launch reads each knob once. */
 int ecamd_tune(const char *key, int value);
 

@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "../host/gf16.hpp"
+#include "../host/tune.hpp"
 #include "ecamd.h"
 #include "ecamd_host.h"
 #include "ecamd_internal.hpp"
@@ -378,7 +379,7 @@ int locate_pairs(const std::vector<int>& A, int K, int R, const PairsTable& t, c
     a.stride = t.stride;
     const int64_t units = (blocksize + 3) >> 2;
     int chunks = static_cast<int>(std::clamp<int64_t>((units + 4095) / 4096, 1, 64)), slots = std::min(nstripes, 4096 / chunks);
-    const int cap = dev_tune("pairs_grid");
+    const int cap = g_tune.pairs_grid;
     if (cap > 0) {
         chunks = std::min(chunks, cap);
         slots = std::min(slots, cap);
@@ -535,17 +536,18 @@ int64_t xor_check_fused(int dev, int k, int m, const uint32_t* masks, const uint
                         uint32_t* d_suspects, void* stream)
 {
     const int n = k + m;
-    if (!dev_tune("xor_check_fused") || n <= 4 || n > kXorCheckMaxFrags || m > kXorCheckMaxRows || nstripes <= 0) return 0;
-    const int knob_threads = dev_tune("xor_check_threads");
+    if (!g_tune.xor_check_fused || n <= 4 || n > kXorCheckMaxFrags || m > kXorCheckMaxRows || nstripes <= 0) return 0;
+    const int knob_threads = g_tune.xor_check_threads;
     const int threads = knob_threads ? knob_threads : 64;
     const int64_t tile = static_cast<int64_t>(threads) * 16;
     const int64_t cover = blocksize / tile * tile;
     if (cover == 0 || stripe_stride < 0) return 0;
     if ((n - 1) * frag_stride + blocksize >= (int64_t(1) << 31)) return 0;
     const uint64_t tps = static_cast<uint64_t>(cover / tile);
-    const int wgs = dev_tune("xor_wgs") > 0 ? dev_tune("xor_wgs") : 3;
+    const int wgs_knob = g_tune.xor_wgs;
+    const int wgs = wgs_knob > 0 ? wgs_knob : 3;
     const uint64_t slots = static_cast<uint64_t>(dev_cu_count(dev)) * static_cast<uint64_t>(wgs);
-    const uint64_t limit = static_cast<uint64_t>(std::max(dev_tune("xor_tiles_per_slot"), 0)) * static_cast<uint64_t>(256 / threads);
+    const uint64_t limit = static_cast<uint64_t>(std::max<int>(g_tune.xor_tiles_per_slot, 0)) * static_cast<uint64_t>(256 / threads);
     const int per = launch_stripes(nstripes, tps, slots, limit);
     if (tps * static_cast<uint64_t>(per) > 0x7fffffffull) return 0;
     XorCheckArgs a{};

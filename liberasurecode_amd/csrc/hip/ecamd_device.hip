@@ -24,6 +24,7 @@
 #include "../host/crc.hpp"
 #include "../host/gf16.hpp"
 #include "../host/tables.hpp"
+#include "../host/tune.hpp"
 #include "ecamd.h"
 #include "ecamd_host.h"
 #include "ecamd_internal.hpp"
@@ -63,25 +64,6 @@ struct DeviceInfo {
 std::mutex g_dev_mu;
 int g_ndev = -1;
 std::vector<DeviceInfo> g_dev;
-
-// $ECAMD_TUNE="key=value,key=value": knobs applied once, before the first call touches a device --
-// so a profiler or an A/B can run an unmodified command (bench.py) with other launch shapes.
-void tune_from_env()
-{
-    const char* env = std::getenv("ECAMD_TUNE");
-    if (!env) return;
-    std::string all(env);
-    size_t pos = 0;
-    while (pos < all.size()) {
-        size_t end = all.find(',', pos);
-        if (end == std::string::npos) end = all.size();
-        const std::string kv = all.substr(pos, end - pos);
-        const size_t eq = kv.find('=');
-        if (eq != std::string::npos && eq > 0)
-            (void)ecamd_tune(kv.substr(0, eq).c_str(), std::atoi(kv.c_str() + eq + 1));
-        pos = end + 1;
-    }
-}
 
 int ensure_device(int* dev_out)
 {
@@ -179,275 +161,6 @@ int cu_count(int dev)
 
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
-// Launch-geometry knobs (0 = automatic).  Set through ecamd_tune() for sweeps; defaults are the
-// measured best on MI355X ("Tuning").
-// A launch knob: written by ecamd_tune from any thread, read by launches on others (each launch
-// reads each knob once; every setting gives bit-identical results, only the launch shape changes).
-// gf16_small_kernel for launches up to 4096 chunks (64 KiB per fragment, one stripe):
-// DESIGN.md §6 (per-call objects of a few KiB).
-constexpr int kSmallChunksDefault = 4096;
-constexpr int kMultiStreamsMax = 4;  // decode_multi fan-out: the caller's stream + 3 pool streams
-
-struct Knob {
-    std::atomic<int> v;
-    explicit Knob(int x) : v(x) {}
-    operator int() const { return v.load(std::memory_order_relaxed); }
-    Knob& operator=(int x)
-    {
-        v.store(x, std::memory_order_relaxed);
-        return *this;
-    }
-};
-
-constexpr int kFrameCrcNibDefault = 0;
-constexpr int kFrameCrcBsDefault = 1;
-// 1-2-output maps of at least 8 inputs take the one-wave bitsliced kernel: C3 (k = 10) single
-// reconstruct of a data / parity fragment 0.685 / 0.690 -> 0.750 / 0.774 of 8 TB/s, decode of 1 / 2
-// lost 0.687 / 0.688 -> 0.770 / 0.750; C5 (k = 20) reconstruct 0.692 -> 0.806; C2 (k = 4) keeps its
-// 8 KiB tables (0.80 against 0.70 bitsliced) (tools/bs_wave_ab.py c3ncap c5ncap2 c2n,
-// profiles/r05_ab_ncap.log, r05_ab_narrow.log)
-constexpr int kBsNarrowMinKDefault = 8;
-
-// Defaults of the one-wave crc form's knobs (frame_crc_wave*).
-struct CrcWaveDefaults {
-    int w, pos, per, pf, big;
-};
-// 4 waves per workgroup, 2 position sets (68 KiB of LDS: 2 workgroups, 8 waves per CU), one tile per
-// wave, the next input's 4 chunks prefetched: against the 16 KiB-tile crc variant in the same runs
-// C3 0.687 -> 0.704, Swift segments 0.591 -> 0.638, C5 0.599 -> 0.674 (profiles/r05_ab_crcwave_c5b.log;
-// 12 waves per CU, 1 or 4 position sets and longer runs per wave all lose: r05_ab_crcwave_*.log)
-constexpr CrcWaveDefaults kCrcWave{4, 2, 1, 4, 0};
-
-struct Tuning {
-    Knob threads{0};     // threads per workgroup of the gf16 kernel
-    Knob wgs_per_cu{0};  // resident workgroups per CU the grid is sized for
-    Knob nt{1};          // 1: non-temporal global loads/stores in the gf16 kernel (+7% on MI355X)
-    Knob nib{0};         // gf16 kernel: 1 = nibble tables (4 conflict-free lookups per word)
-    Knob crc_bits{5};    // CRC32 kernel piece tables: 4 nibble, 8 byte, 5..7 byte tables for the first
-                         // bits-4 dwords of a piece (5 measured best with crc_pos, tools/frame_bench.py)
-    Knob crc_wgs{0};     // CRC32 kernel: resident 512-thread workgroups per CU (0 = by LDS)
-    Knob frame_crc_fused{1};  // framed encode with CRC32: codec + checksums in one launch
-    Knob frame_copy_padded{1};  // framed encode: copy-through also for objects shorter than k*bs
-    Knob frame_crc_wgs{0};    //   512-thread workgroups per CU (0 = 2)
-    Knob frame_crc_units{0};  //   work units (stripe ranges) per CU to aim for (0 = 4)
-    Knob frame_crc_mb{0};     //   piece dwords on byte tables (1, 2 or 4; 0 = 1), 4-output passes
-    Knob frame_crc_bs{kFrameCrcBsDefault};  //   1: the bitsliced kernel's crc variant for maps of
-                                            //   <= 4 outputs (< 0: default)
-    Knob frame_crc_bs_wgs{0}; //   its grid in 256-thread workgroups per CU (0: one per work unit)
-    Knob frame_crc_pos{0};    //   its CRC position table sets (1, 2, 4: one gap step per that many pieces;
-                              //   0 = by shape: 1 with the lane-shift fold of <= 4 outputs (its 32 KiB
-                              //   of lane tables leave room for 1 set at 3 workgroups per CU), else 2
-                              //   (profiles/r03_fused_sweep_pos.log, r03_fused_sweep_lane.log)
-    Knob frame_crc_nib{kFrameCrcNibDefault};  //   1: the codec on nibble tables (conflict-free LDS;
-                                              //   tools/frame_bench.py --fused-sweep); < 0: default
-    Knob frame_unfused{0};  // framed encode: 1 = always split then encode (A/B against copy-through)
-    Knob frame_copy_stream{1};  // object <-> payload copies: streaming 32-bit-offset kernels (0: the
-                                //   first-version per-16-byte kernels, A/B and fallback)
-    Knob crc_gap_bits{8};   // CRC32 kernel at crc_bits 4: field width of the gap / butterfly maps
-    Knob crc_span_kib{128}; // CRC32 kernel: KiB of payload per wave (span), multiple of 4
-    Knob crc_pos{1};        // CRC32 kernel: position-specific piece tables (one gap step per 4 pieces)
-    Knob stream{1};         // strided gf16 launches: gf16_stream_kernel (buffer loads, pipelined)
-    Knob stream_ch{1};      //   16-byte chunks per lane (1, 2; W = 8 always 1)
-    Knob small_chunks{kSmallChunksDefault};  // strided launches of at most this many 16-byte chunks
-                            //   per output row at a uniform pitch: gf16_small_kernel (0 = never)
-    Knob small_crc_dbg{0};  //   development A/B of the fused small-launch CRC (SmallArgs::crc_dbg)
-    Knob small_stage{1};    //   gf16_small_kernel: stage the inputs into LDS with 16-byte loads first
-                            //   (one stripe, 16-byte pitch; 1 = whenever the LDS holds them, 0 = never)
-    Knob small_lane{0};     //   gf16_small_kernel: bytes per lane (2, 4 or 16; 0: 2 when one workgroup
-                            //   covers the pass that way, else 4 -- DESIGN.md §6)
-    Knob xor_wgs{0};        // xor_stream_kernel: 256-thread workgroups per CU (0 = by shape, see
-                            // launch_xor)
-    Knob grid_mult{0};      // stream launches: workgroups per resident slot (0: 2 for 4-output
-                            //   passes of at most 64 tiles per slot, else 1; tools/grid_sweep.py,
-                            //   tools/c3_size_sweep.py)
-    Knob multi_list{1};     // heterogeneous decode: stripe-list stream launches (else pointer tables)
-    Knob multi_streams{1};  //   its per-pattern launches spread over this many streams (1: all on the
-                            //   caller's; the others fork from it and join back, decode_multi_pool)
-    Knob bitslice{1};       // 8-output passes: run-time compiled bitsliced kernel (ecamd_jit.hip);
-                            //   1 once compiled (LDS tables meanwhile), 2 wait for the compile, 0 off
-    Knob bitslice_min_rows{5};   // fewest outputs of a row group that take the bitsliced kernel
-    Knob bitslice_entries{256};  // matrices with a loaded bitsliced kernel kept (LRU beyond)
-    Knob bitslice_depth{0}; //   inputs straight into registers (0, default) or through a per-wave
-                            //   LDS ring 2 / 4 deep; tools/c5_prof.py C5_MODES A/B
-    Knob stream_hybrid{1};  //   8-output passes: one input in 4 looks its hi table up via L1
-    Knob stream_order{0};   //   tile order: bit 0 contiguous range per workgroup, bit 1 XCD-grouped
-    Knob stream_realign{0}; //   copy-through inputs at offsets that are not multiples of 16: 2 = one aligned
-                            //   load per lane, the window's second chunk from the next lane (DPP); 1 = aligned
-                            //   loads realigned in registers (gf16_realign_kernel), 0 = unaligned 16-byte
-                            //   loads -- measured faster (Swift segments 1.366 vs 1.444 ms, C3 + 10 B
-                            //   1.226 vs 1.281 ms, tools/realign_ab.py, profiles/r03_realign_ab.log)
-    Knob stream_chunk{-1};  //   > 0: grid of one workgroup per `stream_chunk` consecutive tiles (the
-                            //   dispatcher balancing them, as bs_grid), 0: grid-stride over the
-                            //   slots; -1 (default): 2 when the tables are at most 8 KiB (C2 encode
-                            //   0.783 -> 0.803 of 8 TB/s), else 0 -- a workgroup per range reloads
-                            //   the tables (C3's 40 KiB: 0.739 -> 0.64-0.69, tools/stream_chunk_ab.py);
-                            //   1 instead of 2 when the outputs are not consecutive fragments (C2's
-                            //   mixed decode {0,4}: 0.721 -> 0.764, while encode / {0,1} lose 0.5-0.8%
-                            //   with 1, tools/c3_tile_ab.py c2 chunk, profiles/r03_c2_chunk_ab.log;
-                            //   the policy in place: mixed 0.718 -> 0.768, r03_c2_chunk_ab2.log)
-    Knob stream_nib{0};     //   nibble tables: 0 never, 1 always, 2 for 8-output passes only
-    Knob stream_pf{0};      //   next group's loads issued before the lookups (1) or after (0);
-                            //   0 measured faster at C2 / C3 / C5 (tools/stream_sweep.py)
-    Knob tiles_per_slot{0};   // stream passes: most tiles per resident workgroup in one launch
-                              //   (longer batches run as several launches; 0: 32 for 4-output
-                              //   passes, else 64; tools/slot_sweep.py)
-    Knob bs_grid{1};              // ecamd_bs_kernel: 1 = one workgroup per tile, the dispatcher balancing
-                                  //   them (C5 encode 0.705 -> 0.748, rebuild-8 0.688 -> 0.738 of 8 TB/s,
-                                  //   tools/c5_grid_ab.py); 0 = grid-stride over the resident slots
-    Knob frame_crc_lane{1};       // bitsliced crc variant (<= 4 outputs): lane-shift fold with 1
-                                  //   position set (C3 0.659 -> 0.686 of 8 TB/s against the butterfly
-                                  //   with 2 sets, profiles/r03_fused_sweep_lane.log)
-    Knob frame_crc_bs_nib{0};     // bitsliced crc variant: nibble piece tables (bitslice.hpp crc_nib)
-    Knob bs_prefetch{2};          // one-wave bitsliced copy-through kernel: chunks (0, 2, 4) of the next input
-                                  //   loaded before the current input's copy stores and network
-                                  //   (BitsliceStyle::prefetch). On GFX9 vmcnt retires loads and stores in
-                                  //   issue order, so without it every input's loads also wait for the
-                                  //   previous input's copy stores: C3 framed encode 0.657 -> 0.721, decode-join
-                                  //   0.637 -> 0.747 (profiles/r04_frame_wave_pf_ab2.log). Plain maps: neutral
-                                  //   (profiles/r04_bs_prefetch_ab.log), so they keep none
-    Knob bs_late_copy{1};         // 16 KiB-tile bitsliced copy-through (5-8 outputs): 1 (default) = each input's copy
-                                  //   stores after its network and the next input's loads, from the planes
-                                  //   transposed back (BitsliceStyle prefetch 1): C5 framed encode 0.660 ->
-                                  //   0.670, decode-join of 8 data 0.629 -> 0.710 (profiles/r04_late_copy_ab.log)
-    Knob bs_copy_ring{0};         // one-wave copy-through maps read through an LDS ring of 2 / 4 inputs (0: registers)
-    Knob bs_realign{1};           // bitsliced copy-through / crc kernels reading object chunks at offsets that are not
-                                  //   multiples of 16: 1 = aligned loads + the neighbour lane's chunk (DPP),
-                                  //   realigned in registers (BitsliceStyle::in_shift); 0 = unaligned loads
-    Knob frame_join_align{2};     // systematic framed decode: a payload's join tiles start on object chunks that
-                                  //   are multiples of the tile (whole aligned lines per workgroup): 1 always,
-                                  //   2 (default) on the realigning path (bs % 16 != 0): Swift segments
-                                  //   0.754 -> 0.766, C3 + 6 B 0.689 -> 0.792 of 8 TB/s with 4 KiB tiles
-                                  //   (profiles/r04_join_align_ab.log); 0 never
-    Knob frame_xor_copy{1};       // framed flat-XOR encode: copy-through XOR launch over the whole tiles (object
-                                  //   chunks -> data payloads + parity in one pass); decode with data lost:
-                                  //   the decode-join (lost data straight into the objects); 0 = split + XOR,
-                                  //   decode in place + join
-    Knob frame_tail_bs{1};        // framed RS encode of objects that do not fill the payloads: the payloads'
-                                  //   rest past the whole tiles by a streaming split + the plain bitsliced
-                                  //   encode of their last 4 KiB tiles (ecamd_frame_api.hip encode_tail);
-                                  //   0 = the LDS-table copy-through launch
-    Knob frame_tail_tiles{1};     // encode_tail: whole 4 KiB tiles past `from` by the copy-through launch of that
-                                  //   range first (split + re-encoded tiles only for the last partial one); 0 off
-    Knob frame_tail_fork{1};      // framed encode of objects that do not fill the payloads: the payloads' rest
-                                  //   past the whole tiles (codec, and its CRC32) on a side stream forked from
-                                  //   the caller's, beside the launch of the whole tiles, with exact ranges (no
-                                  //   byte written by both); 1 = without checksum and a rest of 1-4 KiB, 2 = always,
-                                  //   0 = after it on the caller's stream (ecamd_frame_api.hip fork_tail).  The
-                                  //   same for the LDS-table rest of a copy-through map (decode-join): map_apply_copy
-    Knob frame_crc_prefetch{0};   // bitsliced crc variant (<= 4 outputs; the 8-output form has no registers left):
-                                  //   chunks (0, 2, 4) of the next input loaded before the current input's
-                                  //   copy stores (BitsliceStyle::prefetch)
-    Knob frame_crc_cover{1};      // framed CRC32 encode of payloads that are not whole 16 KiB tiles (Swift's
-                                  //   1 MiB segments): the crc variant over the whole tiles + tail codec +
-                                  //   tail CRC (ecamd_frame_api.hip encode_crc_cover); 0 = codec + CRC pass
-    Knob frame_copy_dpp{1};       // framed split / join stream kernels, realigning path (bs % 16 != 0): 1 =
-                                  //   each lane's second aligned chunk from its neighbour lane (DPP
-                                  //   wave_shl:1, the last lane's own load issued in the same burst);
-                                  //   0 = two loads per lane.  Swift segment join 0.704 -> 0.726 of 8 TB/s,
-                                  //   C3 + 6 B 0.724 -> 0.715 (noise level; profiles/r04_copy_dpp_ab2.log)
-    Knob frame_copy_threads{0};   // framed split / join stream kernels: lanes per tile (64 / 128 / 256; 0 = by
-                                  //   shape: 64 for 16-byte-multiple payloads, else 256, ecamd_frame_api.hip)
-    Knob frame_copy_u{0};         //   and 16-byte chunks per lane (1 / 4; 0 = 1)
-    Knob frame_copy_grid{1};      // framed split / join stream kernels: 1 = one workgroup per tile
-                                  //   (systematic join, Swift 1 MiB segments 0.83 -> 0.91 of the copy
-                                  //   probe, C3 0.97 -> 1.02; tools/frame_bench.py), 0 = 8 per CU
-    Knob xor_threads{0};          // xor_stream_kernel: threads per workgroup = the tile (16 B per lane per
-                                  //   fragment): 64 / 128 / 256 for 1 / 2 / 4 KiB tiles; 0 = by shape: 64
-                                  //   for passes of more than 4 inputs over fragments of kXorNarrowMin and
-                                  //   more, else 256.  One-wave 1 KiB tiles at 1 MiB: (10,5,3) encode
-                                  //   0.722-0.728 -> 0.790-0.792 of 8 TB/s, (10,6,4) 0.784-0.786 ->
-                                  //   0.797-0.800, decodes 5-7% faster; (3,3,3) at 1 MiB and (10,6,4) at
-                                  //   64 KiB 0.7-3.5% slower, 4 KiB fragments 2% slower (two runs,
-                                  //   tools/xor_threads_ab.py, profiles/r03_xor_threads_ab1.log, _ab2.log)
-    Knob xor_grid{1};             // xor_stream_kernel: 1 = one workgroup per tile, 0 = resident slots
-    Knob xor_check_fused{1};      // ecamd_xor_check / ecamd_xor_locate: whole tiles through xor_check_kernel
-                                  //   (ecamd_check.hip); 0 = the generic stage only
-    Knob xor_check_threads{0};    // xor_check_kernel: 64 / 256 threads per workgroup = 1 / 4 KiB tiles; 0 = the
-                                  //   default, 64 at every size (measured: xor_check_fused in ecamd_check.hip,
-                                  //   DESIGN.md "Flat XOR: fused check, locate and scrub")
-    Knob pairs_grid{0};           // locate_pairs_kernel (ecamd_check.hip): > 0 caps both grid dimensions (chunks
-                                  //   per stripe, stripe slots), so tests make both grid-stride loops iterate
-    Knob bs_wave{1};              // ecamd_bs_kernel in one-wave workgroups of 4 KiB tiles (64 lanes x 4
-                                  //   chunks 1 KiB apart, built with a 2-wave register budget) instead of
-                                  //   4-wave 16 KiB tiles: 1 (default) row groups of bs_wave_min_rows..4
-                                  //   outputs take it (below bitslice_min_rows); 2 every bitsliced launch
-                                  //   too (5..8 outputs: slower, C5 rebuild 0.738 -> 0.690); 0 never.
-                                  //   Plain maps only (not copy-through / crc).  C3, three interleaved
-                                  //   rounds (tools/bs_wave_ab.py, profiles/r04_bs_wave_ab1.log): encode
-                                  //   0.733 -> 0.746, decode {0,1,2,3} 0.734 -> 0.742, mixed {0,5,10,13}
-                                  //   0.700 -> 0.753 of 8 TB/s against the LDS-table stream kernel
-    Knob bs_wave_min_rows{3};     //   fewest outputs of a row group that bs_wave 1 moves (1..4)
-    Knob bs_narrow_min_k{kBsNarrowMinKDefault};  //   > 0: row groups of 1-2 outputs over at least this many inputs
-                                                 //   take it too
-    Knob bs_wave_wmin{0};         //   one-wave forms: amdgpu_waves_per_eu min / max and a scheduling barrier after
-    Knob bs_wave_wmax{0};         //   each input's network (BsOcc, host/bitslice.hpp); 0 / < 0: by R (wave_occ)
-    Knob bs_wave_barrier{-1};
-    Knob bs_wave_depth{0};        //   one-wave plain maps: inputs by LDS-DMA through a per-wave ring 2 / 4 inputs
-                                  //   deep (the next input's loads in flight during the network, no VGPRs held
-                                  //   for them); 0 = straight into registers (the ring measured 1-4% slower)
-    // Resident workgroups per CU (> 0: a cap below what the registers allow, by a dynamic LDS share that
-    // tops the kernel's own LDS up to 160 KiB / N, cap_lds; 0: none):
-    Knob bs_wave_per_cu{-1};      //   one-wave plain maps (< 0: 7 below 20 fragments per tile, else none): C3 encode /
-                                  //   decode / mixed 0.749 / 0.746 / 0.756 -> 0.812 / 0.796 / 0.783 of 8 TB/s at
-                                  //   7, 0.70 / 0.67 / 0.66 at 6, 0.73-0.75 at 8 (tools/bs_wave_ab.py c3cap c3cap2
-                                  //   c3cap3, profiles/r05_ab_cap.log, r05_ab_cap2.log, r05_ab_cap3.log); a
-                                  //   21-fragment tile (C5 single reconstruct) runs best uncapped at 8: 0.813 /
-                                  //   0.822 against 0.799 / 0.806 at 7 (r05_ab_cap3.log, r05_ab_ncap.log)
-    Knob bs_copy_per_cu{6};       //   one-wave copy-through maps whose inputs are aligned: C3 framed encode
-                                  //   0.708 -> 0.758, decode-join 0.734 -> 0.783 at 6 (7: 0.725 / 0.746; Swift
-                                  //   segments' decode-join 0.636 -> 0.651; tools/frame_wave_ab.py cap,
-                                  //   profiles/r05_ab_copycap.log)
-    Knob bs_copy_realign_per_cu{0};  //   ... and realigned inputs (Swift's segment encode: 0.664 uncapped, 0.652 at 6)
-    Knob bs_tile_threads{256};    //   ecamd_bs_kernel, plain 5-8-output maps: lanes per workgroup (128 / 256 / 512:
-                                  //   8 / 16 / 32 KiB tiles)
-    Knob bs_tile_per_cu{0};       //   ecamd_bs_kernel in 16 KiB tiles (5-8 outputs)
-    Knob check_per_cu{-1};        //   the check form in one-wave tiles (ecamd_rs_check; < 0: as bs_wave_per_cu's policy,
-                                  //   by the K + R fragments a tile reads; DESIGN.md "Consistency check")
-    Knob frame_crc_per_cu{0};     //   the bitsliced crc variant (framed CRC32 encode)
-    Knob bs_plain_prefetch{0};    //   one-wave plain maps: chunks (0 / 2 / 4) of the next input loaded before each network
-    Knob frame_copy_per_cu{0};    //   framed split / join streaming kernels (copy_lds, ecamd_frame_api.hip)
-    Knob xor_per_cu{-1};          //   xor_stream_kernel: < 0 by shape (launch_xor)
-    Knob bs_wave_copy{1};         //   copy-through maps (framed encode / decode-join): 1 (default) too, 2 only
-                                  //   when their inputs start at offsets that are not multiples of 16, 0 never.
-                                  //   With the prefetch (bs_prefetch) the one-wave form beats the LDS-table
-                                  //   stream kernel: C3 framed encode 0.694 -> 0.721, decode-join 0.739 ->
-                                  //   0.747, Swift decode-join 0.571 -> 0.603; Swift encode ties (0.64;
-                                  //   profiles/r04_frame_wave_pf_ab2.log)
-    Knob bs_tiles_per_slot{16};   // ecamd_bs_kernel: the same for bitsliced passes (0: one launch;
-                                  //   16: C5 x 128 stripes +3%, tools/bs_slot_sweep.py)
-    Knob bs_store_through{-1};    // ecamd_bs_kernel, plain one-wave maps: outputs stored write-through (sc0 sc1 nt: the
-                                  //   lines go straight to memory, not through an L2 allocation evicted later); 1
-                                  //   always, 0 never (the kernel as it was), < 0 by shape: maps of 2 to 4 outputs
-                                  //   (bs_form).  Measured on 4-output maps -- C3 step (encode + decode {0,1,2,3})
-                                  //   1.5-1.8% faster at 256 and 64 stripes, mixed decode +0.8% -- and on one 2-output
-                                  //   decode (+0.7%); 3-output maps sit between and were not measured, 5-8-output
-                                  //   maps in one-wave tiles (bs_wave 2) neither and keep nt; 1-output maps ran
-                                  //   0.6-1.3% SLOWER and keep nt.  The per-shape figures are medians of five
-                                  //   interleaved rounds each (tools/launch_timeline.py ab / other,
-                                  //   profiles/r07_launch_knob_ab.json; DESIGN.md §4 "Per-launch cost")
-    Knob xor_tiles_per_slot{32};  // xor_stream_kernel: the same for flat XOR passes (0: one launch;
-                                  //   32 measured best with the 12-wave geometry, (3,3,3) C1 +2%,
-                                  //   tools/xor_geom_sweep.py; 64 before)
-    // framed CRC32 encode on the crc variant in one-wave 4 KiB tiles (bitslice.cpp CW form): waves per
-    // workgroup (0: the 16 KiB-tile crc variant), position sets (1 / 2 / 4), tiles per wave, waves
-    // per SIMD of its register budget (0: 3), chunks (0 / 2 / 4) of the next input loaded with each input's
-    Knob frame_crc_wave{kCrcWave.w};
-    Knob frame_crc_wave_pos{kCrcWave.pos};
-    Knob frame_crc_wave_per{kCrcWave.per};
-    Knob frame_crc_wave_wpe{0};
-    Knob frame_crc_wave_big{kCrcWave.big};  //   % of the tiles in runs of frame_crc_wave_per per wave
-    Knob frame_crc_wave_pf{kCrcWave.pf};
-    Knob frame_crc_wave_mb{4};      //   piece dwords on byte tables (the rest on nibble tables)
-    Knob frame_crc_wave_mix{0};     //   no scheduling barrier between an input's CRC lookups and its network
-    Knob frame_crc_wave_l1{0};      //   a piece's last dword through its byte tables in global memory (the
-                                    //   vector L1 as a second lookup engine beside the LDS; round 6 A/B)
-    Knob frame_crc_wave_strict{0};  // tests: a framed CRC32 encode the one-wave crc form declines fails
-    Knob scatter_lanes{0};  // ecamd_scatter_fragments: one copy lane per destination device for
-                            //   peers (0), for every destination incl. local ones (1, exercises the
-                            //   fork / join on one-GPU boxes), or none: all on the caller's stream (2)
-};
-Tuning g_tune;
-
 }  // namespace
 
 namespace ecamd {
@@ -463,57 +176,6 @@ int dev_fail(int code, const char* fmt, ...)
     va_end(ap);
     g_err = buf;
     return code;
-}
-int dev_tune(const char* key)
-{
-    const std::string k(key);
-    if (k == "xor_check_fused") return g_tune.xor_check_fused;
-    if (k == "xor_check_threads") return g_tune.xor_check_threads;
-    if (k == "pairs_grid") return g_tune.pairs_grid;
-    if (k == "xor_tiles_per_slot") return g_tune.xor_tiles_per_slot;
-    if (k == "xor_wgs") return g_tune.xor_wgs;
-    if (k == "crc_bits") return g_tune.crc_bits;
-    if (k == "crc_wgs") return g_tune.crc_wgs;
-    if (k == "frame_copy_grid") return g_tune.frame_copy_grid;
-    if (k == "frame_copy_per_cu") return g_tune.frame_copy_per_cu;
-    if (k == "frame_copy_dpp") return g_tune.frame_copy_dpp;
-    if (k == "frame_crc_lane") return g_tune.frame_crc_lane;
-    if (k == "frame_crc_bs_nib") return g_tune.frame_crc_bs_nib;
-    if (k == "xor_threads") return g_tune.xor_threads;
-    if (k == "frame_copy_threads") return g_tune.frame_copy_threads;
-    if (k == "frame_copy_u") return g_tune.frame_copy_u;
-    if (k == "frame_unfused") return g_tune.frame_unfused;
-    if (k == "crc_gap_bits") return g_tune.crc_gap_bits;
-    if (k == "crc_pos") return g_tune.crc_pos;
-    if (k == "crc_span_kib") return g_tune.crc_span_kib;
-    if (k == "frame_crc_fused") return g_tune.frame_crc_fused;
-    if (k == "frame_copy_padded") return g_tune.frame_copy_padded;
-    if (k == "frame_copy_stream") return g_tune.frame_copy_stream;
-    if (k == "frame_crc_wgs") return g_tune.frame_crc_wgs;
-    if (k == "frame_crc_units") return g_tune.frame_crc_units;
-    if (k == "frame_crc_mb") return g_tune.frame_crc_mb;
-    if (k == "frame_crc_nib") return g_tune.frame_crc_nib;
-    if (k == "frame_crc_bs") return g_tune.frame_crc_bs;
-    if (k == "frame_crc_cover") return g_tune.frame_crc_cover;
-    if (k == "frame_crc_prefetch") return g_tune.frame_crc_prefetch;
-    if (k == "frame_crc_wave") return g_tune.frame_crc_wave;
-    if (k == "frame_crc_wave_pos") return g_tune.frame_crc_wave_pos;
-    if (k == "frame_crc_wave_strict") return g_tune.frame_crc_wave_strict;
-    if (k == "frame_crc_wave_mix") return g_tune.frame_crc_wave_mix;
-    if (k == "frame_crc_wave_mb") return g_tune.frame_crc_wave_mb;
-    if (k == "frame_crc_wave_l1") return g_tune.frame_crc_wave_l1;
-    if (k == "frame_tail_bs") return g_tune.frame_tail_bs;
-    if (k == "frame_tail_fork") return g_tune.frame_tail_fork;
-    if (k == "frame_tail_tiles") return g_tune.frame_tail_tiles;
-    if (k == "frame_xor_copy") return g_tune.frame_xor_copy;
-    if (k == "frame_join_align") return g_tune.frame_join_align;
-    if (k == "bs_realign") return g_tune.bs_realign;
-    if (k == "bs_copy_ring") return g_tune.bs_copy_ring;
-    if (k == "bs_late_copy") return g_tune.bs_late_copy;
-    if (k == "bs_prefetch") return g_tune.bs_prefetch;
-    if (k == "frame_crc_pos") return g_tune.frame_crc_pos;
-    if (k == "bitslice_entries") return g_tune.bitslice_entries;
-    return 0;
 }
 
 int launch_stripes(int nstripes, uint64_t tiles_per_stripe, uint64_t slots, uint64_t limit)
@@ -2505,7 +2167,8 @@ int rs_encode_copy_crc(int k, int m, const void* obj, int64_t obj_stride, void* 
     a.ntiles = a.tiles_per_stripe * static_cast<uint32_t>(nstripes);
     FusedCrcArgs c{d_img, d_partial, q, static_cast<int>(bs / kTile) / q, k + m};
     const int64_t units = static_cast<int64_t>(nstripes) * q;
-    const int want = dev_tune("frame_crc_wgs") > 0 ? dev_tune("frame_crc_wgs") : 2;
+    const int wgs_knob = g_tune.frame_crc_wgs;
+    const int want = wgs_knob > 0 ? wgs_knob : 2;
     const int wgs = std::max<int>(1, std::min<int>(want, kLdsBytes / static_cast<int>(lds)));
     const dim3 grid(static_cast<unsigned>(std::min<int64_t>(units, static_cast<int64_t>(cu_count(map->device)) * wgs)));
     const dim3 block(kThreads);
@@ -2914,205 +2577,9 @@ int ecamd_map_cache_stats(int64_t* entries, int64_t* bytes, int64_t* limit)
 int ecamd_tune(const char* key, int value)
 {
     if (!key) return fail(ECAMD_EINVAL, "null key");
-    std::string k(key);
-    if (k == "threads") {
-        if (value != 0 && (value < 64 || value > 1024 || value % 64))
-            return fail(ECAMD_EINVAL, "threads must be a multiple of 64 in [64,1024]");
-        g_tune.threads = value;
-    } else if (k == "wgs_per_cu") {
-        g_tune.wgs_per_cu = std::max(0, std::min(value, 8));
-    } else if (k == "nt") {
-        g_tune.nt = value != 0;  // note: the default is 1; ecamd_tune("nt", 0) turns it off
-    } else if (k == "nib") {
-        g_tune.nib = value != 0;
-    } else if (k == "crc_bits") {
-        // 4 nibble tables, 8 byte tables, 5..7 byte tables for the first bits-4 dwords of a piece
-        g_tune.crc_bits = (value >= 4 && value <= 8) ? value : 5;  // 0 restores the default (5)
-    } else if (k == "crc_wgs") {
-        g_tune.crc_wgs = std::max(0, std::min(value, 1 << 16));  // > resident: one workgroup per 8 spans
-    } else if (k == "crc_gap_bits") {
-        g_tune.crc_gap_bits = value == 4 ? 4 : 8;  // 0 restores the default (8)
-    } else if (k == "crc_span_kib") {
-        g_tune.crc_span_kib = (value >= 4 && value <= 256) ? value / 4 * 4 : 128;  // 0: default
-    } else if (k == "crc_pos") {
-        g_tune.crc_pos = value;  // 0 off, anything else on
-    } else if (k == "frame_crc_wgs") {
-        g_tune.frame_crc_wgs = std::max(0, std::min(value, 8));
-    } else if (k == "frame_crc_mb") {
-        g_tune.frame_crc_mb = value;
-    } else if (k == "frame_crc_bs") {
-        g_tune.frame_crc_bs = value < 0 ? kFrameCrcBsDefault : value;
-    } else if (k == "frame_crc_pos") {
-        g_tune.frame_crc_pos = value <= 0 ? 0 : value >= 4 ? 4 : value >= 2 ? 2 : 1;  // <= 0: by shape
-    } else if (k == "frame_crc_bs_wgs") {
-        g_tune.frame_crc_bs_wgs = std::max(0, std::min(value, 8));
-    } else if (k == "frame_crc_nib") {
-        g_tune.frame_crc_nib = value < 0 ? kFrameCrcNibDefault : (value != 0);
-    } else if (k == "frame_crc_units") {
-        g_tune.frame_crc_units = std::max(0, std::min(value, 64));
-    } else if (k == "frame_copy_padded") {
-        g_tune.frame_copy_padded = value;  // 0 off, anything else on
-    } else if (k == "frame_copy_stream") {
-        g_tune.frame_copy_stream = value;
-    } else if (k == "frame_crc_fused") {
-        g_tune.frame_crc_fused = value;  // 0 off, anything else on
-    } else if (k == "frame_join_align") {
-        g_tune.frame_join_align = value < 0 ? 2 : std::min(value, 2);  // < 0: the default (2)
-    } else if (k == "frame_xor_copy") {
-        g_tune.frame_xor_copy = value;  // 0 off, anything else on
-    } else if (k == "frame_tail_tiles") {
-        g_tune.frame_tail_tiles = value < 0 ? 1 : value != 0;  // < 0: the default (1)
-    } else if (k == "frame_tail_fork") {
-        g_tune.frame_tail_fork = value < 0 ? 1 : std::min(value, 2);  // < 0: the default (1)
-    } else if (k == "frame_tail_bs") {
-        g_tune.frame_tail_bs = value;  // 0 off, anything else on
-    } else if (k == "frame_crc_prefetch") {
-        g_tune.frame_crc_prefetch = value == 2 || value == 4 ? value : 0;
-    } else if (k == "frame_crc_cover") {
-        g_tune.frame_crc_cover = value;  // 0 off, anything else on
-    } else if (k == "bs_prefetch") {
-        g_tune.bs_prefetch = value < 0 ? 2 : value == 2 || value == 4 ? value : 0;  // < 0: the default (2)
-    } else if (k == "bs_late_copy") {
-        g_tune.bs_late_copy = value < 0 ? 1 : value > 0 ? 1 : 0;  // < 0: the default (1)
-    } else if (k == "bs_copy_ring") {
-        g_tune.bs_copy_ring = value >= 4 ? 4 : value >= 2 ? 2 : 0;
-    } else if (k == "bs_realign") {
-        g_tune.bs_realign = value < 0 ? 1 : value != 0;  // < 0: the default (1)
-    } else if (k == "frame_unfused") {
-        g_tune.frame_unfused = value != 0;
-    } else if (k == "stream") {
-        g_tune.stream = value != 0;
-    } else if (k == "small_lane") {
-        g_tune.small_lane = value == 16 || value == 4 || value == 2 ? value : 0;
-    } else if (k == "small_crc_dbg") {
-        g_tune.small_crc_dbg = value < 0 ? 0 : value;
-    } else if (k == "small_stage") {
-        g_tune.small_stage = value < 0 ? 1 : value != 0;
-    } else if (k == "small_chunks") {
-        g_tune.small_chunks = value < 0 ? kSmallChunksDefault : value;
-    } else if (k == "stream_ch") {
-        g_tune.stream_ch = value == 2 ? 2 : 1;
-    } else if (k == "xor_wgs") {
-        g_tune.xor_wgs = std::max(0, std::min(value, 8));
-    } else if (k == "grid_mult") {
-        g_tune.grid_mult = std::max(0, std::min(value, 64));
-    } else if (k == "multi_list") {
-        g_tune.multi_list = value;
-    } else if (k == "multi_streams") {
-        g_tune.multi_streams = value < 1 ? 1 : std::min(value, kMultiStreamsMax);
-    } else if (k == "bitslice") {
-        g_tune.bitslice = value;
-    } else if (k == "bitslice_min_rows") {
-        g_tune.bitslice_min_rows = value >= 1 && value <= 8 ? value : 5;  // 0 restores the default
-    } else if (k == "bitslice_entries") {
-        g_tune.bitslice_entries = value >= 1 && value <= 4096 ? value : 256;  // 0 restores the default
-    } else if (k == "bitslice_depth") {
-        g_tune.bitslice_depth = value >= 4 ? 4 : value >= 2 ? 2 : 0;
-    } else if (k == "stream_hybrid") {
-        g_tune.stream_hybrid = value;
-    } else if (k == "stream_realign") {
-        g_tune.stream_realign = value >= 2 ? 2 : value > 0 ? 1 : 0;  // < 0: the default (0)
-    } else if (k == "stream_chunk") {
-        g_tune.stream_chunk = std::max(-1, std::min(value, 1 << 16));  // -1: by table size
-    } else if (k == "stream_order") {
-        g_tune.stream_order = std::max(0, std::min(value, 3));
-    } else if (k == "stream_nib") {
-        g_tune.stream_nib = std::max(0, std::min(value, 2));
-    } else if (k == "stream_pf") {
-        g_tune.stream_pf = value != 0;
-    } else if (k == "tiles_per_slot") {
-        g_tune.tiles_per_slot = value >= 1 && value <= (1 << 20) ? value : 0;  // 0 restores the default
-    } else if (k == "bs_grid") {
-        g_tune.bs_grid = value < 0 ? 1 : value != 0;
-    } else if (k == "frame_crc_lane") {
-        g_tune.frame_crc_lane = value != 0;  // < 0: the default (1)
-    } else if (k == "frame_crc_bs_nib") {
-        g_tune.frame_crc_bs_nib = value > 0;  // <= 0: the default (byte tables)
-    } else if (k == "frame_copy_dpp") {
-        g_tune.frame_copy_dpp = value < 0 ? 1 : value != 0;  // < 0: the default (1)
-    } else if (k == "frame_copy_grid") {
-        g_tune.frame_copy_grid = value != 0;  // < 0: the default (1)
-    } else if (k == "frame_copy_threads") {
-        g_tune.frame_copy_threads = value == 64 || value == 128 || value == 256 ? value : 0;
-    } else if (k == "frame_copy_u") {
-        g_tune.frame_copy_u = value == 1 || value == 4 ? value : 0;
-    } else if (k == "xor_threads") {
-        g_tune.xor_threads = value == 64 || value == 128 || value == 256 ? value : 0;  // else by shape
-    } else if (k == "xor_check_fused") {
-        g_tune.xor_check_fused = value != 0;  // < 0: the default (1)
-    } else if (k == "xor_check_threads") {
-        g_tune.xor_check_threads = value == 64 || value == 256 ? value : 0;  // else the default (64)
-    } else if (k == "pairs_grid") {
-        g_tune.pairs_grid = std::max(0, std::min(value, 65535));  // <= 0: the default (by shape)
-    } else if (k == "xor_grid") {
-        g_tune.xor_grid = value != 0;  // < 0: the default (1)
-    } else if (k == "bs_wave") {
-        g_tune.bs_wave = value < 0 ? 1 : std::min(value, 2);  // < 0: the default (1)
-    } else if (k == "bs_wave_copy") {
-        g_tune.bs_wave_copy = value < 0 ? 1 : std::min(value, 2);  // < 0: the default (1)
-    } else if (k == "bs_wave_min_rows") {
-        g_tune.bs_wave_min_rows = value >= 1 && value <= 4 ? value : 3;  // else the default
-    } else if (k == "bs_narrow_min_k") {
-        g_tune.bs_narrow_min_k = value < 0 ? kBsNarrowMinKDefault : std::min(value, 33);
-    } else if (k == "bs_wave_wmin") {
-        g_tune.bs_wave_wmin = value >= 1 && value <= 8 ? value : 0;
-    } else if (k == "bs_wave_wmax") {
-        g_tune.bs_wave_wmax = value >= 1 && value <= 8 ? value : 0;
-    } else if (k == "bs_wave_barrier") {
-        g_tune.bs_wave_barrier = value < 0 ? -1 : value != 0;
-    } else if (k == "bs_wave_per_cu") {
-        g_tune.bs_wave_per_cu = value < 0 ? -1 : std::min(value, 32);  // < 0: by shape
-    } else if (k == "bs_copy_per_cu") {
-        g_tune.bs_copy_per_cu = value < 0 ? 6 : std::min(value, 32);  // < 0: the default
-    } else if (k == "bs_plain_prefetch") {
-        g_tune.bs_plain_prefetch = value == 2 || value == 4 ? value : 0;
-    } else if (k == "frame_copy_per_cu") {
-        g_tune.frame_copy_per_cu = value < 0 ? 0 : std::min(value, 32);
-    } else if (k == "bs_tile_threads") {
-        g_tune.bs_tile_threads = value == 128 || value == 512 ? value : 256;
-    } else if (k == "check_per_cu") {
-        g_tune.check_per_cu = value < 0 ? -1 : std::min(value, 32);  // < 0: by shape
-    } else if (k == "bs_tile_per_cu") {
-        g_tune.bs_tile_per_cu = value < 0 ? 0 : std::min(value, 32);
-    } else if (k == "frame_crc_per_cu") {
-        g_tune.frame_crc_per_cu = value < 0 ? 0 : std::min(value, 32);
-    } else if (k == "bs_copy_realign_per_cu") {
-        g_tune.bs_copy_realign_per_cu = value < 0 ? 0 : std::min(value, 32);
-    } else if (k == "xor_per_cu") {
-        g_tune.xor_per_cu = value < 0 ? -1 : std::min(value, 32);
-    } else if (k == "bs_wave_depth") {
-        g_tune.bs_wave_depth = value == 2 || value == 4 ? value : 0;
-    } else if (k == "bs_tiles_per_slot") {
-        g_tune.bs_tiles_per_slot = value >= 0 && value <= (1 << 20) ? value : 16;
-    } else if (k == "bs_store_through") {
-        g_tune.bs_store_through = value < 0 ? -1 : value > 0 ? 1 : 0;
-    } else if (k == "xor_tiles_per_slot") {
-        g_tune.xor_tiles_per_slot = value >= 0 && value <= (1 << 20) ? value : 32;
-    } else if (k == "frame_crc_wave") {  // (negative: the defaults)
-        g_tune.frame_crc_wave = value < 0 ? kCrcWave.w : std::min(value, 15);
-    } else if (k == "frame_crc_wave_pos") {
-        g_tune.frame_crc_wave_pos = value <= 0 ? kCrcWave.pos : value >= 4 ? 4 : value >= 2 ? 2 : 1;
-    } else if (k == "frame_crc_wave_per") {
-        g_tune.frame_crc_wave_per = value <= 0 ? kCrcWave.per : std::min(value, 1 << 16);
-    } else if (k == "frame_crc_wave_big") {
-        g_tune.frame_crc_wave_big = value < 0 ? kCrcWave.big : std::min(value, 100);
-    } else if (k == "frame_crc_wave_pf") {
-        g_tune.frame_crc_wave_pf = value < 0 ? kCrcWave.pf : value >= 2 && value <= 4 ? value : 0;  // (3: 2 inputs ahead)
-    } else if (k == "frame_crc_wave_mb") {
-        g_tune.frame_crc_wave_mb = value <= 0 ? 4 : std::min(value, 4);
-    } else if (k == "frame_crc_wave_mix") {
-        g_tune.frame_crc_wave_mix = value > 0 ? 1 : 0;
-    } else if (k == "frame_crc_wave_l1") {
-        g_tune.frame_crc_wave_l1 = value > 0 ? 1 : 0;
-    } else if (k == "frame_crc_wave_strict") {
-        g_tune.frame_crc_wave_strict = value > 0 ? 1 : 0;
-    } else if (k == "frame_crc_wave_wpe") {
-        g_tune.frame_crc_wave_wpe = std::max(0, std::min(value, 8));
-    } else if (k == "scatter_lanes") {
-        g_tune.scatter_lanes = std::max(0, std::min(value, 2));
-    } else {
-        return fail(ECAMD_EINVAL, "unknown tuning key %s", key);
-    }
+    const TuneSet r = tune_set(g_tune, key, value);  // the knobs and their rules: host/tune_knobs.def
+    if (!r.knob) return fail(ECAMD_EINVAL, "unknown tuning key %s", key);
+    if (!r.stored) return fail(ECAMD_EINVAL, "%s must be %s", key, r.knob->must);
     return 0;
 }
 

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../host/crc.hpp"
+#include "../host/tune.hpp"
 #include "ecamd.h"
 #include "ecamd_frame.hpp"
 #include "ecamd_host.h"
@@ -71,7 +72,7 @@ int image(int dev, bool legacy, int B, int J, int G, bool pos, const DevImage** 
 // LDS share of 160 KiB / N; 0 = none).
 size_t copy_lds()
 {
-    const int n = dev_tune("frame_copy_per_cu");
+    const int n = g_tune.frame_copy_per_cu;
     return n > 0 ? (size_t(163840) / static_cast<size_t>(n)) & ~size_t(511) : 0;
 }
 
@@ -89,7 +90,7 @@ int scratch(int dev, void* stream, size_t words, uint32_t** out, int slot = 0)
 // (profiles/r04_tail_fork_ab1.log .. _ab3.log).
 bool fork_tail(int64_t rest, bool crc)
 {
-    const int knob = dev_tune("frame_tail_fork");
+    const int knob = g_tune.frame_tail_fork;
     return rest > 0 && (knob == 2 || (knob == 1 && !crc && rest >= 1024 && rest < 4096));
 }
 
@@ -150,11 +151,12 @@ int run_crc(int dev, bool legacy, bool with_crc, const uint8_t* base, int64_t ss
 {
     const int64_t items = static_cast<int64_t>(nfrag) * nstripes;
     if (items == 0) return 0;
-    const int B = dev_tune("crc_bits");  // 4 .. 8 (host/crc.cpp build_crc_image)
-    const int G = B != 4 ? 8 : (dev_tune("crc_gap_bits") == 4 ? 4 : 8);
-    const bool pos = dev_tune("crc_pos") != 0 && G == 8;
+    const int B = g_tune.crc_bits;  // 4 .. 8 (host/crc.cpp build_crc_image)
+    const int G = B != 4 ? 8 : (g_tune.crc_gap_bits == 4 ? 4 : 8);
+    const bool pos = g_tune.crc_pos != 0 && G == 8;
     const int64_t body = len & ~int64_t(15);
-    const int jmax = dev_tune("crc_span_kib") > 0 ? dev_tune("crc_span_kib") : 16;  // KiB per span
+    const int span_knob = g_tune.crc_span_kib;
+    const int jmax = span_knob > 0 ? span_knob : 16;  // KiB per span
     int J = static_cast<int>(std::min<int64_t>(jmax, std::max<int64_t>(4, ((body / 1024 + 3) / 4) * 4)));
     const DevImage* di = nullptr;
     int rc = image(dev, legacy, B, J, G, pos, &di);
@@ -182,7 +184,7 @@ int run_crc(int dev, bool legacy, bool with_crc, const uint8_t* base, int64_t ss
         const int64_t waves = items * a.nspans;
         rc = scratch(dev, stream, static_cast<size_t>(waves), &partial);
         if (rc) return rc;
-        int wpc = dev_tune("crc_wgs");
+        int wpc = g_tune.crc_wgs;
         // Measured on MI355X (C3 payloads, 3.5 GiB): B=8 at 2 workgroups/CU 6.35 TB/s, 3: 5.94,
         // 4 (LDS-capped to 3): 5.95; B=4 at 4: 5.36 ("Framing"); the default B=5 with
         // position tables at 8 (twice the resident grid): 0.703 -> 0.724 of 8 TB/s against 4
@@ -270,7 +272,7 @@ CopyShape copy_shape(int64_t bs)
 {
     CopyShape c;
     c.threads = bs % 16 == 0 ? 64 : 256;
-    const int t = dev_tune("frame_copy_threads"), u = dev_tune("frame_copy_u");
+    const int t = g_tune.frame_copy_threads, u = g_tune.frame_copy_u;
     if (t == 64 || t == 128 || t == 256) c.threads = t;
     if (u == 1 || u == 4) c.u = u;
     return c;
@@ -282,7 +284,7 @@ int copy_grid(int dev, int64_t chunks_per_frag, int k, int nstripes, const CopyS
 {
     const int64_t per = static_cast<int64_t>(cs.threads) * cs.u;
     const int64_t tiles = (chunks_per_frag + per - 1) / per * k * static_cast<int64_t>(nstripes);
-    const int64_t cap = dev_tune("frame_copy_grid") ? (int64_t{1} << 30) : static_cast<int64_t>(dev_cu_count(dev)) * 8;
+    const int64_t cap = g_tune.frame_copy_grid ? (int64_t{1} << 30) : static_cast<int64_t>(dev_cu_count(dev)) * 8;
     return static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(tiles, cap)));
 }
 
@@ -380,7 +382,8 @@ int fused_image(int dev, bool legacy, int mb, const uint32_t** out, int tile = 8
 // unit per stripe: 0.51 of 8 TB/s instead of 0.6x).
 int fused_ranges(int dev, int64_t tiles, int nstripes, int default_per_cu)
 {
-    const int64_t per_cu = dev_tune("frame_crc_units") > 0 ? dev_tune("frame_crc_units") : default_per_cu;
+    const int units_knob = g_tune.frame_crc_units;
+    const int64_t per_cu = units_knob > 0 ? units_knob : default_per_cu;
     const int64_t want = per_cu * dev_cu_count(dev);
     for (int64_t q = 1; q < tiles; q++)
         if (tiles % q == 0 && static_cast<int64_t>(nstripes) * q >= want) return static_cast<int>(q);
@@ -436,12 +439,12 @@ int finalize_ranges(int dev, const Code& c, bool legacy, uint64_t obj_size, uint
 // finalize_ranges takes those.  crc_wave_form: the crc_pos flags of the form (0: not this form).
 int crc_wave_form(const Code& c, int64_t cover)
 {
-    int cw = dev_tune("frame_crc_wave");
+    int cw = g_tune.frame_crc_wave;
     if (cw <= 0 || cover <= 0 || cover % 4096) return 0;
     if (c.m > 4) cw = std::min(cw, 8);  // (5-8 outputs: built for 2 waves per SIMD)
-    const int nibw = 4 - std::clamp(dev_tune("frame_crc_wave_mb"), 1, 4);  // piece dwords on nibble tables
-    return dev_tune("frame_crc_wave_pos") | 8 | 32 | (cw << 6) | (dev_tune("frame_crc_wave_mix") ? 1024 : 0) |
-           (nibw << 11) | (nibw == 0 && dev_tune("frame_crc_wave_l1") ? 8192 : 0);
+    const int nibw = 4 - std::clamp<int>(g_tune.frame_crc_wave_mb, 1, 4);  // piece dwords on nibble tables
+    return g_tune.frame_crc_wave_pos | 8 | 32 | (cw << 6) | (g_tune.frame_crc_wave_mix ? 1024 : 0) |
+           (nibw << 11) | (nibw == 0 && g_tune.frame_crc_wave_l1 ? 8192 : 0);
 }
 int crc_wave_mb(int wf) { return 4 - ((wf >> 11) & 3); }  // byte-table dwords per piece of the form wf
 int crc_wave_groups(int64_t tps)
@@ -473,7 +476,7 @@ int encode_crc_bitsliced(int dev, const Code& c, bool legacy, const void* obj, i
                          uint64_t obj_size, uint8_t* frags, int64_t ss, int64_t fs, int64_t bs,
                          int nstripes, void* stream)
 {
-    if (dev_tune("frame_crc_bs") == 0 || c.m > 8 || nstripes <= 0) return ECAMD_EINVAL;
+    if (g_tune.frame_crc_bs == 0 || c.m > 8 || nstripes <= 0) return ECAMD_EINVAL;
     if (const int wf = crc_wave_form(c, bs)) {
         const int nf = c.k + c.m;
         const int64_t tps = bs / 4096;
@@ -487,7 +490,7 @@ int encode_crc_bitsliced(int dev, const Code& c, bool legacy, const void* obj, i
         if ((rc = fused_image(dev, legacy, crc_wave_mb(wf), &img, 1024, wf & 7, false))) return rc;
         if ((rc = rs_encode_copy_crc_bs(c.k, c.m, obj, obj_stride, frags + kHeaderBytes, ss, fs, bs, nstripes, img,
                                         tiles, 0, stream, wf)))
-            return rc == ECAMD_EINVAL && dev_tune("frame_crc_wave_strict")
+            return rc == ECAMD_EINVAL && g_tune.frame_crc_wave_strict
                        ? dev_fail(ECAMD_EHIP, "framed encode: the one-wave crc form declined")
                        : rc;
         if ((rc = crc_wave_combine(dev, legacy, tiles, static_cast<int64_t>(nstripes) * nf, nf, tps, g, partial,
@@ -506,10 +509,10 @@ int encode_crc_bitsliced(int dev, const Code& c, bool legacy, const void* obj, i
     if (rc) return rc;
     const uint32_t* img = nullptr;
     // maps of 5-8 outputs always fold with the lane-shift tables (bitslice.cpp fold_each)
-    const bool lane = c.m > 4 || dev_tune("frame_crc_lane") != 0;
-    int npos = dev_tune("frame_crc_pos");
+    const bool lane = c.m > 4 || g_tune.frame_crc_lane != 0;
+    int npos = g_tune.frame_crc_pos;
     if (npos <= 0) npos = lane && c.m <= 4 ? 1 : 2;
-    const bool nib = dev_tune("frame_crc_bs_nib") > 0;
+    const bool nib = g_tune.frame_crc_bs_nib > 0;
     if ((rc = fused_image(dev, legacy, 4, &img, 4096, npos, nib))) return rc;
     rc = rs_encode_copy_crc_bs(c.k, c.m, obj, obj_stride, frags + kHeaderBytes, ss, fs, bs, nstripes, img,
                                partial, q, stream, npos | (lane ? 8 : 0) | (nib ? 16 : 0));
@@ -528,7 +531,7 @@ int split_range(int dev, int k, const void* obj, int64_t obj_stride, uint64_t ob
     const CopyShape cs = copy_shape(bs);
     const dim3 grid(copy_grid(dev, (r16 - from) / 16, k, nstripes, cs)), block(cs.threads);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const bool dpp = dev_tune("frame_copy_dpp") != 0;
+    const bool dpp = g_tune.frame_copy_dpp != 0;
     if (cs.u == 1)
         hipLaunchKernelGGL((dpp ? frame_split_stream_kernel<1, true> : frame_split_stream_kernel<1, false>), grid, block,
                            copy_lds(), st, sa);
@@ -556,13 +559,13 @@ int encode_tail(int dev, const Code& c, const void* obj, int64_t obj_stride, uin
                 int64_t ss, int64_t fs, int64_t bs, int nstripes, int64_t from, void* stream)
 {
     constexpr int64_t kTile = 4096;
-    if (dev_tune("frame_tail_bs") == 0 || from <= 0 || from % 16 || from >= bs ||
-        !copy_fits32(c.k, fs, bs, static_cast<int64_t>(obj_size)) || dev_tune("frame_copy_stream") == 0)
+    if (g_tune.frame_tail_bs == 0 || from <= 0 || from % 16 || from >= bs ||
+        !copy_fits32(c.k, fs, bs, static_cast<int64_t>(obj_size)) || g_tune.frame_copy_stream == 0)
         return ECAMD_EINVAL;
     const int64_t last = static_cast<int64_t>(obj_size) - (c.k - 1) * bs;
     const int64_t c4 = last > 0 ? std::min(bs, last) / kTile * kTile : 0;  // whole 4 KiB tiles of every chunk
     const int64_t r16 = (bs + 15) & ~int64_t(15);
-    const int64_t mid = dev_tune("frame_tail_tiles") != 0 && c4 > from && c4 < bs ? c4 : from;
+    const int64_t mid = g_tune.frame_tail_tiles != 0 && c4 > from && c4 < bs ? c4 : from;
     const int64_t n = (r16 - mid + kTile - 1) / kTile;
     const int64_t t0 = r16 - n * kTile;
     if (t0 < 0) return ECAMD_EINVAL;
@@ -589,7 +592,7 @@ int encode_crc_cover(int dev, const Code& c, bool legacy, const void* obj, int64
                      void* stream)
 {
     const bool xorc = c.backend == kBackendXor;
-    if (dev_tune("frame_crc_cover") == 0 || dev_tune("frame_crc_bs") == 0 || dev_tune("frame_crc_fused") == 0 ||
+    if (g_tune.frame_crc_cover == 0 || g_tune.frame_crc_bs == 0 || g_tune.frame_crc_fused == 0 ||
         c.m > 8 || bs % 2 || nstripes <= 0 || (xorc && !copy_fits32(c.k, fs, bs, static_cast<int64_t>(obj_size))))
         return ECAMD_EINVAL;
     const int64_t last = static_cast<int64_t>(obj_size) - (c.k - 1) * bs;  // bytes of the last data chunk
@@ -611,10 +614,10 @@ int encode_crc_cover(int dev, const Code& c, bool legacy, const void* obj, int64
     if (wf && (rc = scratch(dev, stream, static_cast<size_t>(nstripes) * static_cast<size_t>(tps) * nf, &tiles, 3)))
         return rc;
     const uint32_t* img = nullptr;
-    const bool lane = c.m > 4 || dev_tune("frame_crc_lane") != 0;
-    int npos = dev_tune("frame_crc_pos");
+    const bool lane = c.m > 4 || g_tune.frame_crc_lane != 0;
+    int npos = g_tune.frame_crc_pos;
     if (npos <= 0) npos = lane && c.m <= 4 ? 1 : 2;
-    const bool nib = dev_tune("frame_crc_bs_nib") > 0;
+    const bool nib = g_tune.frame_crc_bs_nib > 0;
     if ((rc = wf ? fused_image(dev, legacy, crc_wave_mb(wf), &img, 1024, wf & 7, false)
                  : fused_image(dev, legacy, 4, &img, 4096, npos, nib)))
         return rc;
@@ -627,7 +630,7 @@ int encode_crc_cover(int dev, const Code& c, bool legacy, const void* obj, int64
                                                     nstripes, img, out, q, stream, pos, cover)
                            : rs_encode_copy_crc_bs(c.k, c.m, obj, obj_stride, frags + kHeaderBytes, ss, fs, bs, nstripes,
                                                    img, out, q, stream, pos, cover);
-        return r == ECAMD_EINVAL && wf && dev_tune("frame_crc_wave_strict")
+        return r == ECAMD_EINVAL && wf && g_tune.frame_crc_wave_strict
                    ? dev_fail(ECAMD_EHIP, "framed encode: the one-wave crc form declined")
                    : r;
     };
@@ -685,7 +688,7 @@ int encode_crc_fused(int dev, const Code& c, bool legacy, const void* obj, int64
                      uint64_t obj_size, uint8_t* frags, int64_t ss, int64_t fs, int64_t bs,
                      int nstripes, void* stream)
 {
-    if (dev_tune("frame_crc_fused") == 0 || bs % 8192 || nstripes <= 0) return ECAMD_EINVAL;
+    if (g_tune.frame_crc_fused == 0 || bs % 8192 || nstripes <= 0) return ECAMD_EINVAL;
     int rc = encode_crc_bitsliced(dev, c, legacy, obj, obj_stride, obj_size, frags, ss, fs, bs, nstripes, stream);
     if (rc != ECAMD_EINVAL) return rc;
     const int q = fused_ranges(dev, bs / 8192, nstripes, 4);
@@ -697,8 +700,8 @@ int encode_crc_fused(int dev, const Code& c, bool legacy, const void* obj, int64
     // all-byte piece tables (16 KiB) measured 4% faster than byte + nibble (MB = 1, 5.5 KiB) in the
     // fused kernel, where the LDS also serves the codec; MB = 1 when the larger image does not fit
     // codec on nibble tables (knob frame_crc_nib): conflict-free lookups and an image 1/8 the size
-    const bool nib = dev_tune("frame_crc_nib") != 0;
-    int mb = dev_tune("frame_crc_mb") == 1 ? 1 : 4;
+    const bool nib = g_tune.frame_crc_nib != 0;
+    int mb = g_tune.frame_crc_mb == 1 ? 1 : 4;
     if (mb == 4 && fused_crc_lds(c.k, c.m, 4, nib) > static_cast<size_t>(kLdsBytes)) mb = 1;
     if ((rc = fused_image(dev, legacy, mb, &img))) return rc;
     rc = rs_encode_copy_crc(c.k, c.m, obj, obj_stride, frags + kHeaderBytes, ss, fs, bs, nstripes, img,
@@ -762,7 +765,7 @@ int ecamd_frame_encode(int backend, int k, int m, int hd, int checksum, const vo
     uint8_t* p0 = frags + kHeaderBytes;
     const bool aligned = a16(d_obj) && obj_stride % 16 == 0 && bs % 16 == 0;
     if (backend == kBackendRs && aligned && static_cast<int64_t>(obj_size) == k * bs &&
-        dev_tune("frame_unfused") == 0) {
+        g_tune.frame_unfused == 0) {
         // The object fills the k payloads exactly (no padding): one launch reads it, copies the
         // data into the payloads and writes the parity (10 MiB read + 14 MiB written per C3
         // stripe instead of a separate split pass) -- with CRC32 checksums, the same launch also
@@ -782,8 +785,8 @@ int ecamd_frame_encode(int backend, int k, int m, int hd, int checksum, const vo
                        frag_stride, kHeaderBytes, k + m, bs, nstripes, nullptr,
                        header_args(c, checksum, bs, obj_size, 0), stream);
     }
-    if (backend == kBackendRs && a16(d_obj) && obj_stride % 16 == 0 && dev_tune("frame_unfused") == 0 &&
-        dev_tune("frame_copy_padded") != 0) {
+    if (backend == kBackendRs && a16(d_obj) && obj_stride % 16 == 0 && g_tune.frame_unfused == 0 &&
+        g_tune.frame_copy_padded != 0) {
         // Objects that do not fill the payloads exactly (any size: Swift's 1 MiB segments give
         // bs = 104858): the same copy-through launch reads each chunk j*bs of the object with
         // unaligned loads and reads zeros past the object's end, so no split pass either; with
@@ -814,7 +817,7 @@ int ecamd_frame_encode(int backend, int k, int m, int hd, int checksum, const vo
                                     static_cast<int64_t>(obj_size), 0, cover);
             const int rj = side_join(dev, stream);
             if (rc || rj || heads) return rc ? rc : rj;
-        } else if (cover > 0 && cover < bs && dev_tune("frame_tail_bs") != 0) {
+        } else if (cover > 0 && cover < bs && g_tune.frame_tail_bs != 0) {
             if ((rc = rs_encode_copy(k, m, d_obj, obj_stride, p0, stripe_stride, frag_stride, bs, nstripes, stream,
                                      static_cast<int64_t>(obj_size), 0, cover)))
                 return rc;
@@ -832,8 +835,8 @@ int ecamd_frame_encode(int backend, int k, int m, int hd, int checksum, const vo
                        frag_stride, kHeaderBytes, k + m, bs, nstripes, nullptr,
                        header_args(c, checksum, bs, obj_size, 0), stream);
     }
-    if (backend == kBackendXor && a16(d_obj) && obj_stride % 16 == 0 && dev_tune("frame_unfused") == 0 &&
-        dev_tune("frame_xor_copy") != 0 && dev_tune("frame_copy_stream") != 0 &&
+    if (backend == kBackendXor && a16(d_obj) && obj_stride % 16 == 0 && g_tune.frame_unfused == 0 &&
+        g_tune.frame_xor_copy != 0 && g_tune.frame_copy_stream != 0 &&
         copy_fits32(k, frag_stride, bs, static_cast<int64_t>(obj_size))) {
         // flat XOR, copy-through (round 4): the whole 4 KiB tiles every object chunk holds in one
         // launch that reads the chunks, writes the data payloads and the parity; the payloads' rest by
@@ -891,10 +894,10 @@ int ecamd_frame_encode(int backend, int k, int m, int hd, int checksum, const vo
     }
     SplitArgs sa{static_cast<const uint8_t*>(d_obj), obj_stride, static_cast<int64_t>(obj_size),
                  frags, stripe_stride, frag_stride, bs, k, nstripes, aligned ? 1 : 0};
-    if (copy_fits32(k, frag_stride, bs, static_cast<int64_t>(obj_size)) && dev_tune("frame_copy_stream") != 0) {
+    if (copy_fits32(k, frag_stride, bs, static_cast<int64_t>(obj_size)) && g_tune.frame_copy_stream != 0) {
         const CopyShape cs = copy_shape(bs);
         const dim3 grid(copy_grid(dev, (bs + 15) / 16, k, nstripes, cs)), block(cs.threads);
-        const bool dpp = dev_tune("frame_copy_dpp") != 0;
+        const bool dpp = g_tune.frame_copy_dpp != 0;
         if (cs.u == 1)
             hipLaunchKernelGGL((dpp ? frame_split_stream_kernel<1, true> : frame_split_stream_kernel<1, false>), grid,
                                block, copy_lds(), st, sa);
@@ -948,8 +951,8 @@ int ecamd_frame_decode(int backend, int k, int m, int hd, const int* missing, vo
     auto* frags = static_cast<uint8_t*>(d_frags);
     uint8_t* p0 = frags + kHeaderBytes;
     if (data_missing && backend == kBackendRs && d_obj && a16(d_obj) && obj_stride % 16 == 0 &&
-        dev_tune("frame_unfused") == 0 &&
-        (static_cast<int64_t>(obj_size) == k * bs || dev_tune("frame_copy_padded") != 0)) {
+        g_tune.frame_unfused == 0 &&
+        (static_cast<int64_t>(obj_size) == k * bs || g_tune.frame_copy_padded != 0)) {
         // One launch: the lost data are computed straight into the objects and the surviving data
         // payloads are copied there as they stream through (no separate join pass); objects of
         // any size (unaligned chunk offsets j*bs, nothing written past an object's end).
@@ -957,8 +960,8 @@ int ecamd_frame_decode(int backend, int k, int m, int hd, const int* missing, vo
                               nstripes, stream, static_cast<int64_t>(obj_size));
     }
     if (data_missing && backend == kBackendXor && d_obj && a16(d_obj) && obj_stride % 16 == 0 &&
-        dev_tune("frame_unfused") == 0 && dev_tune("frame_xor_copy") != 0 &&
-        (static_cast<int64_t>(obj_size) == k * bs || dev_tune("frame_copy_padded") != 0)) {
+        g_tune.frame_unfused == 0 && g_tune.frame_xor_copy != 0 &&
+        (static_cast<int64_t>(obj_size) == k * bs || g_tune.frame_copy_padded != 0)) {
         // flat XOR, as the RS decode-join: the plan is one 0 / 1 matrix over the surviving fragments
         // (lost ones count as zero, as in xor_plan_apply), so the lost data go straight into the
         // objects and the surviving data payloads are copied there by the same launch
@@ -1003,13 +1006,13 @@ int ecamd_frame_decode(int backend, int k, int m, int hd, const int* missing, vo
                 static_cast<int64_t>(obj_size), nstripes,
                 (a16(d_obj) && obj_stride % 16 == 0 && bs % 16 == 0) ? 1 : 0};
     if (copy_fits32(k, frag_stride, bs, static_cast<int64_t>(obj_size)) && bs >= 32 &&
-        dev_tune("frame_copy_stream") != 0) {
+        g_tune.frame_copy_stream != 0) {
         const CopyShape cs = copy_shape(bs);
-        const int ja_knob = dev_tune("frame_join_align");
+        const int ja_knob = g_tune.frame_join_align;
         const int align = (ja_knob == 1 || (ja_knob == 2 && bs % 16)) && a16(d_obj) && obj_stride % 16 == 0 ? 1 : 0;
         const int64_t span = static_cast<int64_t>(cs.threads) * cs.u;
         const dim3 grid(copy_grid(dev, bs / 16 + 2 + (align ? span - 1 : 0), k, nstripes, cs)), block(cs.threads);
-        const bool dpp = dev_tune("frame_copy_dpp") != 0;
+        const bool dpp = g_tune.frame_copy_dpp != 0;
         if (cs.u == 1)
             hipLaunchKernelGGL((dpp ? frame_join_stream_kernel<1, true> : frame_join_stream_kernel<1, false>), grid,
                                block, copy_lds(), static_cast<hipStream_t>(stream), ja, k, align);

@@ -38,7 +38,6 @@ int xor_apply_list(const uint32_t* masks, int R, int K, void* base, int64_t stri
 int dev_ensure(int* dev_out);                       // 0, or ECAMD_ENODEV / ECAMD_EHIP
 int dev_cu_count(int dev);
 int dev_fail(int code, const char* fmt, ...);       // sets ecamd_last_error(), returns code
-int dev_tune(const char* key);                      // current value of an ecamd_tune() knob
 // Stripes per launch of a strided pass split into launches of at most `limit` tiles per resident
 // workgroup (`slots` of them), as even as the stripes allow; limit 0: one launch (for_each_launch in
 // ecamd_device.hip, xor_check_fused in ecamd_check.hip).

@@ -6,7 +6,7 @@
 // never on a caller's thread or in this process: a GPU process that exits while a compile is in
 // flight simply abandons it, and hiprtc's runtime never shares an address space with the GPU
 // work.  Code objects land in a disk cache ($ECAMD_JIT_CACHE, else /tmp/ecamd-jit-<uid>) keyed by
-// a hash of the request and of the generator itself, so later processes load them at once.  Knob "bitslice": 1 (default)
+// a hash of the request and of the generator itself, so later processes load them at once.  Knob bitslice: 1 (default)
 // launches the LDS-table kernel until the code object is ready, 2 waits for it (tests, bench), 0
 // never uses the bitsliced form; ecamd_bitslice_wait() waits for every compile started so far.
 // The check form (ecamd_rs_check: a syndrome map whose kernel writes status bits, no fragments) is one
@@ -38,6 +38,7 @@
 #include <vector>
 
 #include "../host/bitslice.hpp"
+#include "../host/tune.hpp"
 #include "ecamd.h"
 #include "ecamd_internal.hpp"
 
@@ -252,7 +253,7 @@ struct BsEntry {
 std::atomic<long long> g_bs_launches{0};  // bitsliced kernel launches enqueued by this process
 
 // Matrices with a bitsliced kernel (or one on the way), the least recently used evicted past the
-// "bitslice_entries" knob (256); heap objects never destroyed, so no HIP call runs during static
+// bitslice_entries knob (256); heap objects never destroyed, so no HIP call runs during static
 // destruction.
 std::mutex g_jit_mu;  // guards g_jit, g_running, g_clock and every entry
 auto& g_jit = *new std::map<std::vector<int>, std::shared_ptr<BsEntry>>();
@@ -646,7 +647,7 @@ hipFunction_t bitslice_function(int dev, const std::vector<int>& coeff, int R, i
         poll_compile(ep, false);
         if (ep->state == 0) i++;
     }
-    const size_t max_entries = static_cast<size_t>(std::max(1, dev_tune("bitslice_entries")));
+    const size_t max_entries = static_cast<size_t>(std::max<int>(1, g_tune.bitslice_entries));
     while (g_jit.size() >= max_entries && !g_jit.count(key)) {  // evict the least recently used
         auto victim = g_jit.end();
         for (auto it = g_jit.begin(); it != g_jit.end(); ++it)

@@ -8,7 +8,11 @@ byte-equal to the static order's first.
 Measured and rejected (profiles/r02_dyn_sweep_1ctr.log: one counter; r02_dyn_sweep_8ctr.log: one
 counter per XCD): the dynamic order ran 0.52-0.83x the static one at C3 / C2 and its knobs were
 removed from libecamd again; against the current library this script times the static variants
-only (ecamd_tune refuses the unknown keys)."""
+only (ecamd_tune refuses the unknown keys).
+
+The script now stops at the first knob ecamd_tune refuses instead of timing an A/B in which nothing
+changes: with stream_dyn and stream_grab gone ("Dynamic tile order, measured and
+rejected") it is a record of the experiment, not a runnable sweep."""
 import json
 import os
 import statistics
@@ -26,10 +30,17 @@ VARIANTS = [("static_gm1", 0, 1, 0), ("static_gm2", 0, 2, 0), ("dyn_g2", 1, 0, 2
             ("dyn_g4", 1, 0, 4), ("dyn_g8", 1, 0, 8), ("dyn_g16", 1, 0, 16)]
 
 
+def tune(d, key, value):
+    if d.ecamd_tune(key, value) != 0:
+        sys.exit("dyn_sweep: ecamd_tune refuses %s: the knob was removed from libecamd with the rejected "
+                 "dynamic tile order (DESIGN.md, \"Dynamic tile order, measured and rejected\"); "
+                 "nothing to sweep" % key.decode())
+
+
 def set_variant(d, dyn, gm, grab):
-    d.ecamd_tune(b"stream_dyn", dyn)
-    d.ecamd_tune(b"grid_mult", gm)
-    d.ecamd_tune(b"stream_grab", grab)
+    tune(d, b"stream_dyn", dyn)
+    tune(d, b"grid_mult", gm)
+    tune(d, b"stream_grab", grab)
 
 
 def timed(fn, st, n=20, skip=5):
@@ -44,7 +55,8 @@ def timed(fn, st, n=20, skip=5):
 
 def main():
     d = _lib.dev()
-    d.ecamd_tune(b"bitslice", 0)
+    set_variant(d, 0, 2, 0)  # refused: stop before anything is allocated or timed
+    tune(d, b"bitslice", 0)
     cases = [("c3", 128), ("c3", 256), ("c3", 512), ("c3", 1024), ("c2", 4096)]
     if len(sys.argv) > 1:
         cases = [(c.split(":")[0], int(c.split(":")[1])) for c in sys.argv[1:]]
@@ -90,7 +102,7 @@ def main():
                               "rounds": [round(x, 4) for x in ms]}), flush=True)
         lay.buf.free()
     set_variant(d, 0, 0, 0)
-    d.ecamd_tune(b"bitslice", 1)
+    tune(d, b"bitslice", 1)
 
 
 if __name__ == "__main__":

@@ -7,7 +7,11 @@ stripes, interleaved rounds, median of steady passes; outputs checked against th
 Measured and rejected (profiles/r02_overlap_sweep.log): overlapping loses 1-13% except at 8 tiles
 per slot, where the launch boundaries dominate -- a boundary's value is that it starts every
 workgroup in step again, which overlap gives up.  The knob was removed from libecamd again; against
-the current library this script times the in-order variants twice."""
+the current library this script times the in-order variants twice.
+
+The script now stops at the first knob ecamd_tune refuses instead of timing an A/B in which nothing
+changes: with stream_overlap gone ("Measured and rejected around it: running the odd
+launches of a pass on a second stream") it is a record of the experiment, not a runnable sweep."""
 import json
 import os
 import statistics
@@ -25,8 +29,16 @@ LOST = [0, 1, 2, 3]
 VARIANTS = [(ov, lim) for ov in (0, 1) for lim in (8, 16, 32, 64)]
 
 
+def tune(d, key, value):
+    if d.ecamd_tune(key, value) != 0:
+        sys.exit("overlap_sweep: ecamd_tune refuses %s: the knob was removed from libecamd with the rejected "
+                 "overlapped launches (DESIGN.md, \"running the odd launches of a pass on a second stream\"); "
+                 "nothing to sweep" % key.decode())
+
+
 def main():
     d = _lib.dev()
+    tune(d, b"stream_overlap", 0)  # refused: stop before anything is allocated or timed
     st = D.Stream()
     for S in (256, 2048):
         lay = D.Layout.alloc(K + M, F, S)
@@ -38,8 +50,8 @@ def main():
             host = ref.copy()
             host[:, K:] = 0
             for ov, lim in VARIANTS:
-                d.ecamd_tune(b"stream_overlap", ov)
-                d.ecamd_tune(b"tiles_per_slot", lim)
+                tune(d, b"stream_overlap", ov)
+                tune(d, b"tiles_per_slot", lim)
                 lay.upload_stripes(host)
                 D.rs_encode(K, M, lay, stream=st)
                 st.synchronize()
@@ -47,8 +59,8 @@ def main():
         times = {}
         for _ in range(3):
             for v in VARIANTS:
-                d.ecamd_tune(b"stream_overlap", v[0])
-                d.ecamd_tune(b"tiles_per_slot", v[1])
+                tune(d, b"stream_overlap", v[0])
+                tune(d, b"tiles_per_slot", v[1])
                 for op, fn in (("enc", lambda: D.rs_encode(K, M, lay, stream=st)),
                                ("dec", lambda: D.rs_decode(K, M, LOST, lay, stream=st))):
                     ev = [D.Event() for _ in range(13)]
@@ -65,8 +77,8 @@ def main():
                               "ms": round(med, 4), "TBps": round(S * (K + M) * F / (med * 1e-3) / 1e12, 3)}),
                   flush=True)
         lay.buf.free()
-    d.ecamd_tune(b"stream_overlap", 0)
-    d.ecamd_tune(b"tiles_per_slot", 0)
+    tune(d, b"stream_overlap", 0)
+    tune(d, b"tiles_per_slot", 0)
 
 
 if __name__ == "__main__":
