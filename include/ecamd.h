@@ -362,6 +362,54 @@ int ecamd_rs_scrub(int k, int m, void *base, int64_t stripe_stride, int64_t frag
 int ecamd_xor_scrub(int k, int m, int hd, void *base, int64_t stripe_stride, int64_t frag_stride,
                     int64_t blocksize, int nstripes, uint32_t *d_status, uint32_t *d_suspects,
                     int *n_clean, int *n_repaired, int *n_unlocated, void *stream);
+
+/* ---- correct on the device: locate, then repair the located words, all on `stream` ----
+ * ecamd_rs_correct runs ecamd_rs_locate (d_pairs NULL) or ecamd_rs_locate_pairs (d_pairs given) --
+ * d_status, d_suspects, d_pairs and *checked are byte-identical to what those calls write for the same
+ * data; they keep what the locate found and are NOT re-evaluated after the correction -- and then, with
+ * one more launch on the same stream, corrects in place every stripe with exactly one suspect and,
+ * with d_pairs, every stripe without a suspect whose pair word has exactly two bits.  Every other
+ * stripe is not written.  There is no host wait anywhere in the call: no stream synchronise, no copy
+ * to the host, no launch whose shape depends on what the locate found.  (The first call for a (k, m,
+ * missing) uploads its small tables before it enqueues anything, like every cached map.)
+ * The rule: a located error is an error value.  With S_r = stored_r ^ (what the inputs imply for
+ * checked row r), one bad checked fragment c has e = S_c, one bad input j has e = S_0 / A[0][j], and
+ * a pair {a, b} has (e_a, e_b) = inv(M) (S_p, S_q) with M the 2 x 2 minor of the pair plan
+ * (ecamd_rs_correct_map, ecamd_host.h).  correct_kernel reads the K inputs and the one or two pivot
+ * rows of a stripe with work, XORs each non-zero error value into the stored 4-byte unit and writes
+ * nothing else: the result is the fragment ecamd_rs_decode_multi would write, byte for byte, at the
+ * cost of K+1 or K+2 fragment reads and stores to the damaged words only.  A clean stripe costs three
+ * word loads per workgroup that visits it.
+ * `missing` (-1 terminated, may be NULL) makes it work on degraded stripes: the slots of missing
+ * fragments are never read or written, and the remaining bad fragment is located and corrected as far
+ * as the R = m - |missing| checks allow -- the R == 2 and R == 4 caveats of ecamd_rs_locate and
+ * ecamd_rs_locate_pairs apply word for word (a stripe with one bad fragment more than can be detected
+ * may be "corrected" towards a wrong fragment or pair and ends consistent).  A non-NULL d_pairs with
+ * R < 4 is not an error: d_pairs is zeroed and singles are still corrected.
+ * d_counts (4 uint32, device memory, may be NULL) is overwritten with: stripes clean, corrected from
+ * one suspect, corrected from a pair, dirty and not corrected.
+ * ECAMD_EINVAL for everything the locate rejects (bad layout, null d_status / d_suspects, more than m
+ * missing, k+m > 32, odd blocksize); the data, the arrays and d_counts are then untouched.  An empty
+ * batch returns 0 and writes nothing.
+ * Framed fragments (ecamd_frame_encode) are corrected by passing d_frags + 80 as `base`; a repaired
+ * payload again matches the CRC32 its header holds, since the header is not touched and the payload
+ * is the encode's again.
+ * Knob "pairs_grid" > 0 caps both grid dimensions of correct_kernel as well (tests); results do not change. */
+int ecamd_rs_correct(int k, int m, const int *missing, void *base, int64_t stripe_stride, int64_t frag_stride,
+                     int64_t blocksize, int nstripes, uint32_t *d_status, uint32_t *d_suspects,
+                     uint32_t *d_pairs /* may be NULL */, uint32_t *d_counts /* may be NULL */,
+                     uint32_t *checked, void *stream);
+/* The same over ecamd_xor_locate (flat_xor_hd, all fragments present): the kernel runs over the 0/1
+ * parity bitmaps, fragment f's pivot row is the lowest bit of sig[f] (ecamd_xor_check_plan) and every
+ * scale is 1.  ECAMD_EINVAL, everything untouched, for a code init_xor_hd_code rejects and for an odd
+ * blocksize.  The caveat of ecamd_xor_scrub applies: two bad fragments that read as a third are
+ * "corrected" towards it and leave a consistent stripe -- the same bytes ecamd_xor_scrub leaves. */
+int ecamd_xor_correct(int k, int m, int hd, void *base, int64_t stripe_stride, int64_t frag_stride,
+                      int64_t blocksize, int nstripes, uint32_t *d_status, uint32_t *d_suspects,
+                      uint32_t *d_counts /* may be NULL */, void *stream);
+/* Launches of correct_kernel enqueued by this process (one per call with a non-empty batch and at
+ * least one checked fragment). */
+long long ecamd_correct_launches(void);
 /* Fused locate launches enqueued by this process (tests pin which path ran): the bitsliced locate
  * form (rs_vand), and xor_check_kernel's locate form (flat XOR), each counted on its own. */
 long long ecamd_locate_fused_launches(void);

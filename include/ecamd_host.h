@@ -20,6 +20,9 @@
  *   ecamd_rs_locate_pairs_map         the check map with, for every pair of columns of [A | I], two pivot
  *                                     rows and the rows' combinations of them: which two fragments
  *                                     explain a syndrome (no reference counterpart)
+ *   ecamd_rs_correct_map              the check map with, per column and per pair of columns of [A | I],
+ *                                     the pivot row(s) and the inverse that turn a located stripe's
+ *                                     syndromes into error values (no reference counterpart)
  *   ecamd_rs_reconstruct_map          coefficient row of liberasurecode_rs_vand_reconstruct
  *                                     (liberasurecode_rs_vand.c:483-558)
  */
@@ -85,6 +88,27 @@ int ecamd_rs_locate_map(const int *G, int k, int m, const int *missing, int *inp
 int ecamd_rs_locate_pairs_map(const int *G, int k, int m, const int *missing, int *inputs, int *checked,
                               int *coeff, int *ncheck, int *npairs, int *pivots, int *L,
                               int *independent4);
+
+/* Correction plan (ecamd_rs_correct, ecamd.h): what ecamd_rs_check_map returns, plus what turns the
+ * syndromes of a LOCATED stripe into the error values of its bad fragment(s).  Participants as in the
+ * pair plan: the k inputs (0..k-1), then the R = *ncheck checked rows.  With S_r = stored_r ^ sum_j
+ * coeff[r][j] * input_j per 16-bit word:
+ *   participant c: pivot[c] is a row where column c of [coeff | I] is non-zero -- row 0 for an input,
+ *     its own row for a checked fragment -- and scale[c] the inverse of that entry (1 for a checked
+ *     fragment); when c is the only bad fragment its error is e_c = scale[c] * S_pivot[c].
+ *   pair i of a < b, in the pair plan's order (0,1), (0,2), ..., for R >= 2 (*npairs = P(P-1)/2):
+ *     pair_pivots[2i], [2i+1] = rows (p, q) with a non-singular 2 x 2 minor of columns a, b -- where the
+ *     pair plan exists (R >= 4) the very rows ecamd_rs_locate_pairs_map returns -- and minv[4i..4i+3]
+ *     that minor's inverse, row-major:
+ *         e_a = minv[0] * S_p ^ minv[1] * S_q,   e_b = minv[2] * S_p ^ minv[3] * S_q.
+ *     Dependent columns: pivots (-1, -1) and a zero minv.
+ * XORing the error value into the stored word gives the codeword that agrees with every other
+ * participant -- what a decode with that fragment listed as missing writes.  R < 2: *npairs 0.  R == 0:
+ * every pivot -1 and scale 0.  npairs, pair_pivots and minv may be NULL (singles only).  -1 if more
+ * than m missing. */
+int ecamd_rs_correct_map(const int *G, int k, int m, const int *missing, int *inputs, int *checked,
+                         int *coeff, int *ncheck, int *pivot /* k+R */, int *scale /* k+R */,
+                         int *npairs, int *pair_pivots /* 2 per pair */, int *minv /* 4 per pair */);
 
 /* LDS split-table image for rows [row0,row0+width) x inputs [col0,col0+ncols) of the R x K
  * matrix coeff; width in {2,4,8}.  Returns the byte count written (ncols*512*width*2). */

@@ -58,6 +58,8 @@ def host():
         _proto(h, "ecamd_rs_locate_map", C.c_int, [IP, C.c_int, C.c_int, IP, IP, IP, IP, IP, IP])
         _proto(h, "ecamd_rs_locate_pairs_map", C.c_int,
                [IP, C.c_int, C.c_int, IP, IP, IP, IP, IP, IP, IP, IP, IP])
+        _proto(h, "ecamd_rs_correct_map", C.c_int,
+               [IP, C.c_int, C.c_int, IP, IP, IP, IP, IP, IP, IP, IP, IP, IP])
         _proto(h, "ecamd_bitslice_eval", C.c_int,
                [IP, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, IP])
         _proto(h, "ecamd_bitslice_source", C.c_int64,
@@ -163,6 +165,11 @@ def dev():
         _proto(d, "ecamd_rs_scrub_pairs", C.c_int,
                [C.c_int, C.c_int, VP, C.c_int64, C.c_int64, C.c_int64, C.c_int, VP, VP, VP, IP, IP, IP, IP, VP])
         _proto(d, "ecamd_locate_pairs_launches", C.c_longlong, [])
+        _proto(d, "ecamd_rs_correct", C.c_int,
+               [C.c_int, C.c_int, IP, VP, C.c_int64, C.c_int64, C.c_int64, C.c_int, VP, VP, VP, VP, U32P, VP])
+        _proto(d, "ecamd_xor_correct", C.c_int,
+               [C.c_int, C.c_int, C.c_int, VP, C.c_int64, C.c_int64, C.c_int64, C.c_int, VP, VP, VP, VP])
+        _proto(d, "ecamd_correct_launches", C.c_longlong, [])
         _proto(d, "ecamd_locate_fused_launches", C.c_longlong, [])
         _proto(d, "ecamd_xor_check_fused_launches", C.c_longlong, [])
         _proto(d, "ecamd_xor_locate_fused_launches", C.c_longlong, [])

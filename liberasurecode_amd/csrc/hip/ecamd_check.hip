@@ -23,11 +23,19 @@
 // after the finalize, locate_pairs_kernel reads the dirty stripes that have no suspect again and ORs
 // into d_pairs[s] the fragments its words need; pairs_finalize_kernel keeps a word of exactly two
 // bits (DESIGN.md "Two bad fragments").
+//
+// Correct stage (ecamd_rs_correct, ecamd_xor_correct): after the locate or the pair stage,
+// correct_kernel reads the three words of each stripe and XORs the error values of a located fragment
+// or pair into the stored words -- on the same stream, with no host wait (DESIGN.md "Correct on the
+// device").
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <atomic>
+#include <map>
 #include <memory>
+#include <mutex>
 #include <vector>
 
 #include "../host/gf16.hpp"
@@ -403,6 +411,207 @@ int locate_pairs(const std::vector<int>& A, int K, int R, const PairsTable& t, c
     return 0;
 }
 
+// ---- correct on the device: correct_kernel (ecamd_rs_correct, ecamd_xor_correct) ----------------
+// Runs after a locate (or the pair stage), on its results and on the same stream: a located error is an
+// error VALUE.  With S_r = stored_r ^ sum_j A[r][j] * in_j, the one bad participant c of a stripe has
+// e_c = scale[c] * S_pivot[c] in every word, and a located pair {a, b} with pivot rows (p, q) has
+// (e_a, e_b) = inv(M) (S_p, S_q), M the 2 x 2 minor the pair plan picked.  XORing the error value into
+// the stored word gives the codeword that agrees with every other participant -- the fragment a
+// decode would write, byte for byte -- so only the words that are wrong are written.  The table
+// (CorrectTable, ecamd_internal.hpp) is device memory kept with the cached check map.
+struct CorrectArgs {
+    uint8_t* base;  // participant c of stripe s at base + s*stripe_stride + off[c]
+    const uint32_t* status;
+    const uint32_t* suspects;
+    const uint32_t* pairs;  // null: singles only
+    const uint32_t* table;
+    int64_t stripe_stride;
+    int64_t len;  // bytes per fragment, even
+    int64_t off[32];
+    uint32_t cmask[kPairsMaxRows * 16];  // as PairsArgs
+    int32_t nstripes, K, P;
+};
+
+// Syndrome row `row` (wave-uniform) of the lane's unit: Horner over the coefficient bits, as
+// locate_pairs_kernel takes it.  A bit no coefficient of the row has (flat XOR: all but bit 0) costs
+// the doubling only.
+template <int KG>
+__device__ __forceinline__ uint32_t correct_syndrome(const CorrectArgs& a, const uint32_t (&in)[4 * KG], int row,
+                                                     const uint8_t* xs, int64_t u, int64_t whole)
+{
+    uint32_t acc = 0u;
+    for (int b = 15; b >= 0; b--) {
+        const uint32_t hi = acc & 0x80008000u;
+        acc = ((acc & 0x7fff7fffu) << 1) ^ ((hi >> 15) * 0x100bu);
+        const uint32_t m = a.cmask[row * 16 + b];
+        if (m == 0u) continue;
+#pragma unroll
+        for (int j = 0; j < 4 * KG; j++) acc = xor_and(acc, in[j], 0u - ((m >> j) & 1u));
+    }
+    return acc ^ pairs_unit(xs + a.off[a.K + row], u, whole, a.len);
+}
+
+// XOR the non-zero error value e into unit u of the fragment at x: one 4-byte read and store; the
+// last, partial unit byte by byte, so nothing at or past `len` is read or written.
+__device__ __forceinline__ void correct_unit(uint8_t* x, int64_t u, int64_t whole, int64_t len, uint32_t e)
+{
+    if (u < whole) {
+        uint32_t* w = reinterpret_cast<uint32_t*>(x + u * 4);
+        *w ^= e;
+        return;
+    }
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const int64_t q = (whole << 2) + i;
+        if (q < len) x[q] ^= static_cast<uint8_t>(e >> (8 * i));
+    }
+}
+
+// grid (chunks, stripe slots), grid-stride over both, as locate_pairs_kernel; K <= 4*KG.  A workgroup
+// loads status[s], suspects[s] and, when given, pairs[s] -- through readfirstlane, so the case and
+// everything selected by it (table entry, pivot rows, constants, offsets) are scalar -- and goes on only
+// for a stripe with exactly one suspect or, without a suspect, a pair of exactly two bits: a clean
+// batch costs those loads and nothing else.  Per unit of such a stripe: the K inputs in registers, the
+// one or two pivot rows' syndromes, the error value(s) by gf16_mul2 with the stripe's constants; a
+// non-zero error value is XORed into the stored unit of the fragment, a zero one writes nothing.  The
+// only unit a lane writes is the one it read, and no other lane reads it: no synchronisation, no LDS.
+template <int KG>
+__global__ void __launch_bounds__(256) correct_kernel(const CorrectArgs a)
+{
+    const int64_t whole = a.len >> 2, units = (a.len + 3) >> 2;
+    for (int s = static_cast<int>(blockIdx.y); s < a.nstripes; s += static_cast<int>(gridDim.y)) {
+        if (__builtin_amdgcn_readfirstlane(a.status[s]) == 0u) continue;
+        const uint32_t sus = __builtin_amdgcn_readfirstlane(a.suspects[s]);
+        const uint32_t two = sus == 0u && a.pairs ? __builtin_amdgcn_readfirstlane(a.pairs[s]) : 0u;
+        const bool single = sus != 0u && (sus & (sus - 1u)) == 0u;
+        if (!single && __popc(two) != 2) continue;
+        // [f]: participant | pivot row << 8 | scale << 16 of fragment f, all ones when it takes no part
+        uint32_t ea = a.table[__builtin_ctz(single ? sus : two)], eb = 0xffffffffu;
+        int p = static_cast<int>((ea >> 8) & 0xffu), q = 0;
+        uint32_t m01 = ea >> 16, m23 = 0u;  // single: the scale
+        if (!single) {
+            eb = a.table[31 - __builtin_clz(two)];
+            if (ea == 0xffffffffu || eb == 0xffffffffu) continue;
+            if ((ea & 0xffu) > (eb & 0xffu)) {
+                const uint32_t t = ea;
+                ea = eb;
+                eb = t;
+            }
+            // pair i of participants ca < cb at [32 + 3i]: p | q << 8, minv[0] | minv[1] << 16, minv[2] | minv[3] << 16
+            const int ca = static_cast<int>(ea & 0xffu), cb = static_cast<int>(eb & 0xffu);
+            const uint32_t* e = a.table + 32 + 3 * (ca * (2 * a.P - ca - 1) / 2 + (cb - ca - 1));
+            p = static_cast<int>(e[0] & 0xffu);
+            q = static_cast<int>((e[0] >> 8) & 0xffu);
+            m01 = e[1];
+            m23 = e[2];
+        }
+        if (ea == 0xffffffffu || p == 0xff) continue;  // (never: a located fragment takes part, a located pair is independent)
+        uint8_t* xs = a.base + static_cast<int64_t>(s) * a.stripe_stride;
+        uint8_t* xa = xs + a.off[ea & 0xffu];
+        uint8_t* xb = xs + a.off[eb & 0x1fu];
+        for (int64_t u = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x; u < units;
+             u += static_cast<int64_t>(gridDim.x) * 256) {
+            uint32_t in[4 * KG];
+#pragma unroll
+            for (int j = 0; j < 4 * KG; j++) in[j] = j < a.K ? pairs_unit(xs + a.off[j], u, whole, a.len) : 0u;
+            const uint32_t sp = correct_syndrome<KG>(a, in, p, xs, u, whole);
+            if (single) {
+                const uint32_t e = gf16_mul2(m01, sp);
+                if (e != 0u) correct_unit(xa, u, whole, a.len, e);
+            } else {
+                const uint32_t sq = correct_syndrome<KG>(a, in, q, xs, u, whole);
+                const uint32_t e0 = gf16_mul2(m01 & 0xffffu, sp) ^ gf16_mul2(m01 >> 16, sq);
+                const uint32_t e1 = gf16_mul2(m23 & 0xffffu, sp) ^ gf16_mul2(m23 >> 16, sq);
+                if (e0 != 0u) correct_unit(xa, u, whole, a.len, e0);
+                if (e1 != 0u) correct_unit(xb, u, whole, a.len, e1);
+            }
+        }
+    }
+}
+
+// counts[0..3] = stripes clean, with exactly one suspect, with a pair and no suspect, dirty with
+// neither -- the cases correct_kernel tells apart.  One workgroup; the four words are overwritten.
+__global__ void __launch_bounds__(256) correct_counts_kernel(const uint32_t* status, const uint32_t* suspects,
+                                                             const uint32_t* pairs, int n, uint32_t* counts)
+{
+    __shared__ uint32_t part[4][4];
+    uint32_t c[4] = {0u, 0u, 0u, 0u};
+    for (int s = static_cast<int>(threadIdx.x); s < n; s += 256) {
+        const uint32_t sus = suspects[s];
+        if (status[s] == 0u)
+            c[0]++;
+        else if (sus != 0u && (sus & (sus - 1u)) == 0u)
+            c[1]++;
+        else if (sus == 0u && pairs && __popc(pairs[s]) == 2)
+            c[2]++;
+        else
+            c[3]++;
+    }
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        for (int o = 32; o; o >>= 1) c[i] += __shfl_xor(c[i], o);
+        if ((threadIdx.x & 63u) == 0u) part[threadIdx.x >> 6][i] = c[i];
+    }
+    __syncthreads();
+    if (threadIdx.x < 4) counts[threadIdx.x] = part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x];
+}
+
+std::atomic<long long> g_correct_launches{0};
+
+// The correction of one call, after the locate's (or the pair stage's) last kernel on the same
+// stream: correct_kernel and, with d_counts, the counts.  Nothing here waits for the stream or copies
+// to the host -- the case of every stripe is decided on the device.  The grid as locate_pairs, knob
+// pairs_grid included: > 0 caps both dimensions.
+int correct_located(const std::vector<int>& A, int K, int R, const CorrectTable& t, uint8_t* base, int64_t stripe_stride,
+                    const int64_t* in_off, const int64_t* chk_off, int64_t blocksize, int nstripes, const uint32_t* d_status,
+                    const uint32_t* d_suspects, const uint32_t* d_pairs, uint32_t* d_counts, hipStream_t st)
+{
+    if (R >= 1 && R <= kPairsMaxRows && t.dev) {  // no checked fragment: every stripe reads clean
+        CorrectArgs a{};
+        a.base = base;
+        a.status = d_status;
+        a.suspects = d_suspects;
+        a.pairs = t.pairs ? d_pairs : nullptr;
+        a.table = t.dev;
+        a.stripe_stride = stripe_stride;
+        a.len = blocksize;
+        for (int j = 0; j < K; j++) a.off[j] = in_off[j];
+        for (int r = 0; r < R; r++) a.off[K + r] = chk_off[r];
+        for (int r = 0; r < R; r++)
+            for (int j = 0; j < K; j++)
+                for (int b = 0; b < 16; b++)
+                    if ((A[static_cast<size_t>(r) * K + j] >> b) & 1) a.cmask[r * 16 + b] |= 1u << j;
+        a.nstripes = nstripes;
+        a.K = K;
+        a.P = K + R;
+        const int64_t units = (blocksize + 3) >> 2;
+        int chunks = static_cast<int>(std::clamp<int64_t>((units + 4095) / 4096, 1, 64)), slots = std::min(nstripes, 4096 / chunks);
+        const int cap = g_tune.pairs_grid;
+        if (cap > 0) {
+            chunks = std::min(chunks, cap);
+            slots = std::min(slots, cap);
+        }
+        const dim3 grid(static_cast<unsigned>(chunks), static_cast<unsigned>(slots)), block(256);
+        switch ((K + 3) / 4) {  // K <= 31
+        case 1: hipLaunchKernelGGL(correct_kernel<1>, grid, block, 0, st, a); break;
+        case 2: hipLaunchKernelGGL(correct_kernel<2>, grid, block, 0, st, a); break;
+        case 3: hipLaunchKernelGGL(correct_kernel<3>, grid, block, 0, st, a); break;
+        case 4: hipLaunchKernelGGL(correct_kernel<4>, grid, block, 0, st, a); break;
+        case 5: hipLaunchKernelGGL(correct_kernel<5>, grid, block, 0, st, a); break;
+        case 6: hipLaunchKernelGGL(correct_kernel<6>, grid, block, 0, st, a); break;
+        case 7: hipLaunchKernelGGL(correct_kernel<7>, grid, block, 0, st, a); break;
+        default: hipLaunchKernelGGL(correct_kernel<8>, grid, block, 0, st, a); break;
+        }
+        HIP_TRY(hipGetLastError());
+        g_correct_launches.fetch_add(1, std::memory_order_relaxed);
+    }
+    if (d_counts) {
+        hipLaunchKernelGGL(correct_counts_kernel, dim3(1), dim3(256), 0, st, d_status, d_suspects, d_pairs, nstripes, d_counts);
+        HIP_TRY(hipGetLastError());
+    }
+    return 0;
+}
+
 // ---- flat XOR, fused stage: xor_check_kernel -------------------------------------------------
 constexpr int kXorCheckMaxFrags = 28;  // 7 load groups of 4; the accepted codes have k + m <= 26
 constexpr int kXorCheckMaxRows = 6;    // m of the accepted codes: 3, 5, 6
@@ -590,6 +799,7 @@ struct CheckPlan {
     std::vector<uint32_t> sig;       //   xor_check_fused with the signatures of ecamd_xor_check_plan
     CheckMap cached;                 // what A and map point into: the cached check map (rs_vand)
     PairsTable pairs;                //   and its pair table (ecamd_rs_locate_pairs)
+    CorrectTable correct;            // the correction table (ecamd_rs_correct: with the cached map; flat XOR: xor_correct_table)
     std::vector<int> bitmaps;        // or the parity bitmaps as 0 / 1 (flat XOR)
 };
 
@@ -700,10 +910,12 @@ void locate_tables(const std::vector<int>& A, int R, int K, LocateCmpArgs& l)
 
 // The check (d_suspects null) or locate of one validated call: both arrays set, the fused stage over
 // whole tiles, the generic stage over the rest, the finalize step of a locate and, with d_pairs, the
-// pair stage on its results.  StreamUse: the scratch of the stream context outlives the call.
+// pair stage on its results and, with fix_base (the same address as base, writable: ecamd_rs_correct,
+// ecamd_xor_correct), the correction on both.  StreamUse: the scratch of the stream context outlives
+// the call.
 int run_check(int dev, const CheckPlan& p, const void* base, int64_t stripe_stride, int64_t frag_stride,
               int64_t blocksize, int nstripes, uint32_t* d_status, uint32_t* d_suspects, void* stream,
-              uint32_t* d_pairs = nullptr)
+              uint32_t* d_pairs = nullptr, void* fix_base = nullptr, uint32_t* d_counts = nullptr)
 {
     if (nstripes == 0) return 0;
     const StreamUse use(dev, stream);
@@ -762,16 +974,21 @@ int run_check(int dev, const CheckPlan& p, const void* base, int64_t stripe_stri
     hipLaunchKernelGGL(locate_finalize_kernel, dim3(static_cast<unsigned>((nstripes + 255) / 256)), dim3(256), 0, st,
                        d_status, d_suspects, participating, nstripes, d_pairs);
     HIP_TRY(hipGetLastError());
-    if (!d_pairs || R < 4) return 0;  // fewer than four checks leave d_pairs zero
-    return locate_pairs(*p.A, K, R, p.pairs, b, stripe_stride, in_off.data(), chk_off.data(), blocksize, nstripes, d_status,
-                        d_suspects, d_pairs, st);
+    if (d_pairs && R >= 4) {  // fewer than four checks leave d_pairs zero
+        const int prc = locate_pairs(*p.A, K, R, p.pairs, b, stripe_stride, in_off.data(), chk_off.data(), blocksize, nstripes,
+                                     d_status, d_suspects, d_pairs, st);
+        if (prc) return prc;
+    }
+    if (!fix_base) return 0;
+    return correct_located(*p.A, K, R, p.correct, static_cast<uint8_t*>(fix_base), stripe_stride, in_off.data(), chk_off.data(),
+                           blocksize, nstripes, d_status, d_suspects, d_pairs, d_counts, st);
 }
 
 // ecamd_rs_check (locate false), ecamd_rs_locate and ecamd_rs_locate_pairs (pairs true): a bad layout
 // is reported before too many missing fragments, so it is checked before the plan is made.
 int rs_call(bool locate, int k, int m, const int* missing, const void* base, int64_t stripe_stride, int64_t frag_stride,
             int64_t blocksize, int nstripes, uint32_t* d_status, uint32_t* d_suspects, uint32_t* checked, void* stream,
-            bool pairs = false, uint32_t* d_pairs = nullptr)
+            bool pairs = false, uint32_t* d_pairs = nullptr, void* fix_base = nullptr, uint32_t* d_counts = nullptr)
 {
     int dev = 0;
     int rc = dev_ensure(&dev);
@@ -783,6 +1000,7 @@ int rs_call(bool locate, int k, int m, const int* missing, const void* base, int
     CheckPlan p;
     if ((rc = check_map(k, m, missing, p.cached))) return rc;
     if (pairs && (rc = check_map_pairs(p.cached, p.pairs))) return rc;
+    if (fix_base && (rc = check_map_correct(p.cached, p.correct))) return rc;
     p.inputs = *p.cached.inputs;
     p.checked = *p.cached.checked;
     p.A = p.cached.coeff;
@@ -791,12 +1009,43 @@ int rs_call(bool locate, int k, int m, const int* missing, const void* base, int
     for (int f : p.checked) mask |= 1u << f;
     if (checked) *checked = mask;  // for an empty batch too
     return run_check(dev, p, base, stripe_stride, frag_stride, blocksize, nstripes, d_status, locate ? d_suspects : nullptr,
-                     stream, pairs ? d_pairs : nullptr);
+                     stream, pairs ? d_pairs : nullptr, fix_base, d_counts);
+}
+
+// The correction table of a flat XOR code (CorrectTable, ecamd_internal.hpp) from its check plan:
+// fragment f is participant f, its pivot the lowest row of sig[f], every scale 1.  Device memory made
+// at the first call that asks, per (device, k, m, hd), and kept for the life of the process (a few
+// accepted codes, 128 bytes each).
+int xor_correct_table(int dev, int k, int m, int hd, const std::vector<uint32_t>& sig, CorrectTable& out)
+{
+    static std::mutex mu;
+    static std::map<std::array<int, 4>, const uint32_t*> tables;
+    const std::lock_guard<std::mutex> lk(mu);
+    const uint32_t*& slot = tables[{dev, k, m, hd}];
+    if (!slot) {
+        uint32_t tab[32];
+        for (int f = 0; f < 32; f++)
+            tab[f] = f < k + m && sig[static_cast<size_t>(f)]
+                         ? static_cast<uint32_t>(f) | static_cast<uint32_t>(__builtin_ctz(sig[static_cast<size_t>(f)])) << 8 | 1u << 16
+                         : 0xffffffffu;
+        void* d = nullptr;
+        HIP_TRY(hipMalloc(&d, sizeof(tab)));
+        const hipError_t err = hipMemcpy(d, tab, sizeof(tab), hipMemcpyHostToDevice);  // once per code, before anything is enqueued
+        if (err != hipSuccess) {
+            (void)hipFree(d);
+            return dev_fail(ECAMD_EHIP, "correction table: %s", hipGetErrorString(err));
+        }
+        slot = static_cast<const uint32_t*>(d);
+    }
+    out.dev = slot;
+    out.pairs = false;
+    return 0;
 }
 
 // ecamd_xor_check (locate false) and ecamd_xor_locate: the parity bitmaps as a 0 / 1 map over GF(2^16).
 int xor_call(bool locate, int k, int m, int hd, const void* base, int64_t stripe_stride, int64_t frag_stride,
-             int64_t blocksize, int nstripes, uint32_t* d_status, uint32_t* d_suspects, void* stream)
+             int64_t blocksize, int nstripes, uint32_t* d_status, uint32_t* d_suspects, void* stream,
+             void* fix_base = nullptr, uint32_t* d_counts = nullptr)
 {
     int dev = 0;
     int rc = dev_ensure(&dev);
@@ -815,8 +1064,9 @@ int xor_call(bool locate, int k, int m, int hd, const void* base, int64_t stripe
         for (int j = 0; j < k; j++) p.bitmaps.push_back((pb[r] >> j) & 1u);
     }
     p.A = &p.bitmaps;
+    if (fix_base && (rc = xor_correct_table(dev, k, m, hd, p.sig, p.correct))) return rc;
     return run_check(dev, p, base, stripe_stride, frag_stride, blocksize, nstripes, d_status, locate ? d_suspects : nullptr,
-                     stream);
+                     stream, nullptr, fix_base, d_counts);
 }
 
 // The host half of ecamd_rs_scrub, ecamd_xor_scrub and ecamd_rs_scrub_pairs, after the locate: a wait
@@ -979,6 +1229,25 @@ int ecamd_xor_scrub(int k, int m, int hd, void* base, int64_t stripe_stride, int
         return ecamd_xor_decode_multi(k, m, hd, lists, 2, 1, base, stripe_stride, frag_stride, blocksize, nstripes, stream);
     });
 }
+
+// Locate, then correct in place on the same stream: no wait for the stream, no copy to the host, no
+// launch that depends on what the locate found -- correct_kernel reads the per-stripe words itself.
+int ecamd_rs_correct(int k, int m, const int* missing, void* base, int64_t stripe_stride, int64_t frag_stride,
+                     int64_t blocksize, int nstripes, uint32_t* d_status, uint32_t* d_suspects, uint32_t* d_pairs,
+                     uint32_t* d_counts, uint32_t* checked, void* stream)
+{
+    return rs_call(true, k, m, missing, base, stripe_stride, frag_stride, blocksize, nstripes, d_status, d_suspects, checked,
+                   stream, d_pairs != nullptr, d_pairs, base, d_counts);
+}
+
+int ecamd_xor_correct(int k, int m, int hd, void* base, int64_t stripe_stride, int64_t frag_stride, int64_t blocksize,
+                      int nstripes, uint32_t* d_status, uint32_t* d_suspects, uint32_t* d_counts, void* stream)
+{
+    return xor_call(true, k, m, hd, base, stripe_stride, frag_stride, blocksize, nstripes, d_status, d_suspects, stream, base,
+                    d_counts);
+}
+
+long long ecamd_correct_launches(void) { return g_correct_launches.load(std::memory_order_relaxed); }
 
 long long ecamd_xor_check_fused_launches(void) { return g_xor_check_fused.load(std::memory_order_relaxed); }
 long long ecamd_xor_locate_fused_launches(void) { return g_xor_locate_fused.load(std::memory_order_relaxed); }

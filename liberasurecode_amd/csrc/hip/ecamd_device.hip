@@ -1496,9 +1496,15 @@ struct RsEntry {
     PairsTable pairs;
     int pairs_rc = 0;
     void* pairs_dev = nullptr;
+    // and the correction table of check_map_correct, the same way
+    std::once_flag correct_once;
+    CorrectTable correct;
+    int correct_rc = 0;
+    void* correct_dev = nullptr;
     ~RsEntry()
     {
         if (pairs_dev) (void)hipFree(pairs_dev);
+        if (correct_dev) (void)hipFree(correct_dev);
     }
 };
 
@@ -1688,6 +1694,45 @@ int check_map_pairs(const CheckMap& cm, PairsTable& out)
     });
     if (e->pairs_rc) return fail(ECAMD_EHIP, "pair table upload failed");
     out = e->pairs;
+    return 0;
+}
+
+int check_map_correct(const CheckMap& cm, CorrectTable& out)
+{
+    out = CorrectTable();
+    auto* e = const_cast<RsEntry*>(static_cast<const RsEntry*>(cm.hold.get()));
+    if (!e || !cm.coeff) return 0;  // nothing checked: nothing to correct
+    std::call_once(e->correct_once, [e, &cm] {
+        const int K = static_cast<int>(e->inputs.size()), R = static_cast<int>(e->outputs.size());
+        const CorrectPlan plan = rs_correct_plan(*cm.coeff, R, K);
+        const int P = K + R;
+        if (P > 32 || static_cast<int>(plan.pivot.size()) != P) return;
+        std::vector<uint32_t> tab(32, 0xffffffffu);
+        for (int c = 0; c < P; c++) {
+            const int f = c < K ? e->inputs[c] : e->outputs[c - K];
+            if (f < 0 || f >= 32 || plan.pivot[c] < 0) continue;
+            tab[static_cast<size_t>(f)] = static_cast<uint32_t>(c) | static_cast<uint32_t>(plan.pivot[c]) << 8 |
+                                          static_cast<uint32_t>(plan.scale[c]) << 16;
+        }
+        for (int i = 0; i < plan.pairs; i++) {
+            const int p = plan.pair_pivot[static_cast<size_t>(i) * 2], q = plan.pair_pivot[static_cast<size_t>(i) * 2 + 1];
+            const int* w = &plan.minv[static_cast<size_t>(i) * 4];
+            tab.push_back(p < 0 ? 0xffffu : static_cast<uint32_t>(p) | static_cast<uint32_t>(q) << 8);
+            tab.push_back(static_cast<uint32_t>(w[0]) | static_cast<uint32_t>(w[1]) << 16);
+            tab.push_back(static_cast<uint32_t>(w[2]) | static_cast<uint32_t>(w[3]) << 16);
+        }
+        // once per cached map, before anything of the call is enqueued: a few KiB, as the pair table
+        hipError_t err = hipMalloc(&e->correct_dev, tab.size() * sizeof(uint32_t));
+        if (err == hipSuccess) err = hipMemcpy(e->correct_dev, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+        if (err != hipSuccess) {
+            e->correct_rc = fail(ECAMD_EHIP, "correction table: %s", hipGetErrorString(err));
+            return;
+        }
+        e->correct.dev = static_cast<const uint32_t*>(e->correct_dev);
+        e->correct.pairs = plan.pairs > 0;
+    });
+    if (e->correct_rc) return fail(ECAMD_EHIP, "correction table upload failed");
+    out = e->correct;
     return 0;
 }
 

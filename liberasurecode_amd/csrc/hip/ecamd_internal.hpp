@@ -110,6 +110,19 @@ struct PairsTable {
     bool exact = false;
 };
 int check_map_pairs(const CheckMap& cm, PairsTable& out);
+// The correction plan of a cached check map (rs_correct_plan, host/gf16.hpp) as the device table
+// correct_kernel reads, made at the first call that asks for it and kept with the map, like the pair
+// table.  Words [0, 32): for fragment f, participant c | pivot row << 8 | scale << 16, all ones for a
+// fragment that takes no part.  With `pairs` (R >= 2), from word 32 three words per pair of participants
+// a < b in the pair plan's order: pivot row p | pivot row q << 8 (0xff each for dependent columns),
+// minv[0] | minv[1] << 16, minv[2] | minv[3] << 16.  At most 32 + 3 * 496 words; freed with its entry.
+// Flat XOR builds the 32 words alone (ecamd_check.hip): participant f, pivot the lowest bit of sig[f],
+// scale 1.
+struct CorrectTable {
+    const uint32_t* dev = nullptr;
+    bool pairs = false;
+};
+int check_map_correct(const CheckMap& cm, CorrectTable& out);
 // Fused stage of a check or, with d_suspects, of a locate: rows [row0, row0 + nrows) of the R x K
 // matrix A as the syndrome map [A | I] through the check / locate form of the bitsliced kernel, over
 // whole tiles of every stripe.  Input j of stripe s at base + s*stripe_stride + in_off[j], fragment

@@ -285,6 +285,35 @@ int rs_locate_map(const std::vector<int>& G, int k, int m, const std::vector<int
     return 0;
 }
 
+namespace {
+
+// The first two rows (p < q, p ascending, then q) whose 2 x 2 minor of columns ca, cb (R entries each)
+// is non-singular, and that minor's determinant; 0 for dependent columns.  Both the pair plan and the
+// correction plan take their pivots from here, so they describe one minor.
+int pair_minor(const int* ca, const int* cb, int R, int& p, int& q)
+{
+    const GF16& gf = GF16::get();
+    for (p = 0; p < R; p++)
+        for (q = p + 1; q < R; q++) {
+            const int det = gf.mul(ca[p], cb[q]) ^ gf.mul(ca[q], cb[p]);
+            if (det) return det;
+        }
+    return 0;
+}
+
+// Column c of [A | I] at col[c*R..].
+std::vector<int> syndrome_columns(const std::vector<int>& coeff, int R, int K)
+{
+    const int P = K + R;
+    std::vector<int> col(static_cast<size_t>(P) * R, 0);
+    for (int c = 0; c < P; c++)
+        for (int r = 0; r < R; r++)
+            col[static_cast<size_t>(c) * R + r] = c < K ? coeff[static_cast<size_t>(r) * K + c] : (r == c - K);
+    return col;
+}
+
+}  // namespace
+
 PairPlan rs_locate_pairs_plan(const std::vector<int>& coeff, int R, int K)
 {
     PairPlan out;
@@ -293,10 +322,7 @@ PairPlan rs_locate_pairs_plan(const std::vector<int>& coeff, int R, int K)
     if (R < 4 || K <= 0 || coeff.size() != static_cast<size_t>(R) * K) return out;
     const GF16& gf = GF16::get();
     const int P = K + R;
-    std::vector<int> col(static_cast<size_t>(P) * R, 0);  // column c of [A | I] at col[c*R..]
-    for (int c = 0; c < P; c++)
-        for (int r = 0; r < R; r++)
-            col[static_cast<size_t>(c) * R + r] = c < K ? coeff[static_cast<size_t>(r) * K + c] : (r == c - K);
+    const std::vector<int> col = syndrome_columns(coeff, R, K);
     out.pairs = P * (P - 1) / 2;
     out.pivot.assign(static_cast<size_t>(out.pairs) * 2, -1);
     out.L.assign(static_cast<size_t>(out.pairs) * R * 2, 0);
@@ -305,12 +331,9 @@ PairPlan rs_locate_pairs_plan(const std::vector<int>& coeff, int R, int K)
         for (int b = a + 1; b < P; b++, i++) {
             const int* ca = &col[static_cast<size_t>(a) * R];
             const int* cb = &col[static_cast<size_t>(b) * R];
-            int det = 0, p = 0, q = 0;
-            for (p = 0; p < R && !det; p++)
-                for (q = p + 1; q < R && !det; q++) det = gf.mul(ca[p], cb[q]) ^ gf.mul(ca[q], cb[p]);
+            int p = 0, q = 0;
+            const int det = pair_minor(ca, cb, R, p, q);
             if (!det) continue;  // dependent columns: never
-            p--;
-            q--;
             out.pivot[static_cast<size_t>(i) * 2] = p;
             out.pivot[static_cast<size_t>(i) * 2 + 1] = q;
             // (S_p, S_q) = M (x, y) with M = [ca_p cb_p; ca_q cb_q]; S_r = (ca_r, cb_r) inv(M) (S_p, S_q)
@@ -349,6 +372,52 @@ PairPlan rs_locate_pairs_plan(const std::vector<int>& coeff, int R, int K)
                         }
                     }
                 }
+    return out;
+}
+
+CorrectPlan rs_correct_plan(const std::vector<int>& coeff, int R, int K)
+{
+    CorrectPlan out;
+    out.K = K;
+    out.R = R;
+    if (K <= 0 || R < 0 || coeff.size() != static_cast<size_t>(R) * K) return out;
+    const GF16& gf = GF16::get();
+    const int P = K + R;
+    const std::vector<int> col = syndrome_columns(coeff, R, K);
+    out.pivot.assign(static_cast<size_t>(P), -1);
+    out.scale.assign(static_cast<size_t>(P), 0);
+    for (int c = 0; c < P && R > 0; c++) {
+        const int* cc = &col[static_cast<size_t>(c) * R];
+        int p = c < K ? 0 : c - K;
+        // (every entry of a check map of this code is non-zero; a zero takes the first row that is not)
+        for (int r = 0; r < R && !cc[p]; r++)
+            if (cc[r]) p = r;
+        if (!cc[p]) continue;
+        out.pivot[static_cast<size_t>(c)] = p;
+        out.scale[static_cast<size_t>(c)] = gf.inv(cc[p]);
+    }
+    if (R < 2) return out;
+    out.pairs = P * (P - 1) / 2;
+    out.pair_pivot.assign(static_cast<size_t>(out.pairs) * 2, -1);
+    out.minv.assign(static_cast<size_t>(out.pairs) * 4, 0);
+    int i = 0;
+    for (int a = 0; a < P; a++)
+        for (int b = a + 1; b < P; b++, i++) {
+            const int* ca = &col[static_cast<size_t>(a) * R];
+            const int* cb = &col[static_cast<size_t>(b) * R];
+            int p = 0, q = 0;
+            const int det = pair_minor(ca, cb, R, p, q);
+            if (!det) continue;
+            out.pair_pivot[static_cast<size_t>(i) * 2] = p;
+            out.pair_pivot[static_cast<size_t>(i) * 2 + 1] = q;
+            // M = [ca_p cb_p; ca_q cb_q]; in characteristic 2 inv(M) = [cb_q cb_p; ca_q ca_p] / det
+            const int di = gf.inv(det);
+            int* w = &out.minv[static_cast<size_t>(i) * 4];
+            w[0] = gf.mul(cb[q], di);
+            w[1] = gf.mul(cb[p], di);
+            w[2] = gf.mul(ca[q], di);
+            w[3] = gf.mul(ca[p], di);
+        }
     return out;
 }
 

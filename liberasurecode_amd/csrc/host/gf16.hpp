@@ -90,6 +90,23 @@ struct PairPlan {
 };
 PairPlan rs_locate_pairs_plan(const std::vector<int>& coeff, int R, int K);
 
+// Correction plan (ecamd_rs_correct): the error VALUE of a located fragment, from one or two syndrome
+// rows.  Participants as in the pair plan.  Participant c: pivot[c] = a row where column c of [A | I] is
+// non-zero (row 0 for an input, its own row for a checked fragment) and scale[c] = the inverse of that
+// entry (1 for a checked fragment), so that a stripe whose only bad fragment is c has the error
+// e_c = scale[c] * S_pivot[c] in every word.  Pair i of a < b, in the pair plan's order, for R >= 2:
+// pair_pivot[2i..] = the rows (p, q) rs_locate_pairs_plan picks (the same search) and minv[4i..] the
+// row-major inverse of the 2 x 2 minor of columns a, b at those rows:
+//     e_a = minv[0]*S_p ^ minv[1]*S_q,   e_b = minv[2]*S_p ^ minv[3]*S_q.
+// Dependent columns: pivots (-1, -1), minv zero.  R < 2: pairs 0.  R == 0: pivots -1, scales 0.
+struct CorrectPlan {
+    int K = 0, R = 0, pairs = 0;
+    std::vector<int> pivot, scale;  // K + R each
+    std::vector<int> pair_pivot;    // pairs x 2
+    std::vector<int> minv;          // pairs x 4
+};
+CorrectPlan rs_correct_plan(const std::vector<int>& coeff, int R, int K);
+
 // Encode map: inputs 0..k-1, outputs k..k+m-1, generator parity rows.
 FragmentMap rs_encode_map(const std::vector<int>& G, int k, int m);
 

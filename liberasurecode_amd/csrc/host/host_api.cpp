@@ -142,6 +142,30 @@ int ecamd_rs_locate_pairs_map(const int* G, int k, int m, const int* missing, in
     return 0;
 }
 
+int ecamd_rs_correct_map(const int* G, int k, int m, const int* missing, int* inputs, int* checked, int* coeff,
+                         int* ncheck, int* pivot, int* scale, int* npairs, int* pair_pivots, int* minv)
+{
+    if (!G || k <= 0 || m < 0 || !inputs || !ncheck || !pivot || !scale) return -1;
+    std::vector<int> g(G, G + static_cast<size_t>(k + m) * k);
+    FragmentMap fm;
+    if (rs_check_map(g, k, m, minus1_list(missing), fm) != 0) return -1;
+    std::memcpy(inputs, fm.inputs.data(), fm.inputs.size() * sizeof(int));
+    if (!fm.outputs.empty()) {
+        if (!checked || !coeff) return -1;
+        std::memcpy(checked, fm.outputs.data(), fm.outputs.size() * sizeof(int));
+        std::memcpy(coeff, fm.coeff.data(), fm.coeff.size() * sizeof(int));
+    }
+    const int R = static_cast<int>(fm.outputs.size());
+    const CorrectPlan plan = rs_correct_plan(fm.coeff, R, k);
+    std::memcpy(pivot, plan.pivot.data(), plan.pivot.size() * sizeof(int));
+    std::memcpy(scale, plan.scale.data(), plan.scale.size() * sizeof(int));
+    if (pair_pivots && plan.pairs) std::memcpy(pair_pivots, plan.pair_pivot.data(), plan.pair_pivot.size() * sizeof(int));
+    if (minv && plan.pairs) std::memcpy(minv, plan.minv.data(), plan.minv.size() * sizeof(int));
+    *ncheck = R;
+    if (npairs) *npairs = plan.pairs;
+    return 0;
+}
+
 int ecamd_split_tables(const int* coeff, int R, int K, int row0, int width, int col0, int ncols,
                        uint8_t* out)
 {

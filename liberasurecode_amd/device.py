@@ -270,6 +270,43 @@ def rs_scrub_pairs(k, m, lay: Layout, stream=None):
     return status, suspects, pairs, tuple(c.value for c in counts)
 
 
+def _correct(call, lay, stream, what, pairs):
+    """Run call(d_status, d_suspects, d_pairs or None, d_counts), wait for `stream` (or the device) and
+    return (status, suspects, pairs or None, counts)."""
+    n = max(lay.nstripes, 1)
+    buf = DeviceBuffer(12 * n + 16)
+    try:
+        check(dev().ecamd_memset(buf.ptr, 0, 12 * n + 16), "memset")
+        check(call(buf.ptr, buf.ptr + 4 * n, buf.ptr + 8 * n if pairs else None, buf.ptr + 12 * n), what)
+        if stream is not None:
+            stream.synchronize()
+        else:
+            check(dev().ecamd_synchronize(), "synchronize")
+        words = buf.download(12 * n + 16).view(np.uint32)
+        status, suspects, pr = (words[i * n:i * n + lay.nstripes].copy() for i in range(3))
+        return status, suspects, pr if pairs else None, tuple(int(c) for c in words[3 * n:3 * n + 4])
+    finally:
+        buf.free()
+
+
+def rs_correct(k, m, lay: Layout, missing=(), pairs=True, stream=None):
+    """ecamd_rs_correct: locate (with `pairs`, two bad fragments too) and correct the located words in
+    place, all on the stream with no host wait inside the call.  Returns (status, suspects, pairs,
+    counts): the words as rs_locate_pairs / rs_locate write them (pairs None without `pairs`) and counts
+    = (clean, corrected from one suspect, corrected from a pair, dirty and not corrected), after this
+    function's own synchronise.  `missing` fragments' slots are neither read nor written."""
+    return _correct(lambda d, u, p, c: dev().ecamd_rs_correct(
+        k, m, ints(list(missing) + [-1]), lay.buf.ptr, lay.stripe_stride, lay.frag_stride, lay.blocksize,
+        lay.nstripes, d, u, p, c, None, _s(stream)), lay, stream, "rs_correct", pairs)
+
+
+def xor_correct(k, m, hd, lay: Layout, stream=None):
+    """ecamd_xor_correct on full flat_xor_hd stripes: (status, suspects, None, counts) as rs_correct."""
+    return _correct(lambda d, u, p, c: dev().ecamd_xor_correct(
+        k, m, hd, lay.buf.ptr, lay.stripe_stride, lay.frag_stride, lay.blocksize, lay.nstripes, d, u, c,
+        _s(stream)), lay, stream, "xor_correct", False)
+
+
 def xor_scrub(k, m, hd, lay: Layout, stream=None):
     """ecamd_xor_scrub on full flat_xor_hd stripes: locate, then repair in place every stripe with
     exactly one suspect.  Returns (status, suspects, (n_clean, n_repaired, n_unlocated)) as rs_scrub;

@@ -31,11 +31,22 @@ batch -- the pair stage adds one memset, one launch whose workgroups all end aft
 finalize --, (b) with one stripe of 256 holding two damaged words, (c) with two fragments of every
 stripe rewritten, so that every word needs the pair.  With `--tree DIR` of the parent commit it times
 ecamd_rs_locate alone (`--locate-only`: the same on this commit); `--pairs-merge THIS,BEFORE,AFTER` joins this commit's document with two such
-runs of the same session, before and after it: their spread is the margin for (a)."""
+runs of the same session, before and after it: their spread is the margin for (a).
+
+`--correct` measures ecamd_rs_correct (C3 only).  (a) clean batch, HIP events: ecamd_rs_locate_pairs
+against ecamd_rs_correct with pairs (without and with d_counts), alternating.  (b) one stripe of 256 with
+two damaged words and (c) fragments 3 and 12 of every stripe rewritten: ecamd_rs_scrub_pairs against
+ecamd_rs_correct, a host wall clock around call plus stream synchronise -- the scrub's cost includes its
+host half --, the damaged batch copied back from a second device buffer outside the timed region before
+every call.  With `--tree DIR` of the parent commit it times ecamd_rs_locate_pairs and
+ecamd_rs_scrub_pairs alone; `--correct-merge THIS,BEFORE,AFTER` joins this commit's document with two
+such runs of the same session, and `--added-launch-us X` (from a kernel trace of this commit on a clean
+batch) completes the bar of (a): the parent's larger mean, plus the spread between its two runs, plus X."""
 import argparse
 import json
 import os
 import sys
+import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if "--tree" in sys.argv[1:-1]:  # the package and libraries of another built checkout (before the imports below)
@@ -264,6 +275,118 @@ def run_pairs(d, st, reps, n, locate_only=False):
     return out
 
 
+def run_correct(d, st, reps, n):
+    """C3: (a) clean, events: locate_pairs / correct / correct with counts; (b), (c) wall clock around call
+    plus synchronise, the damaged batch restored before every call: scrub_pairs / correct."""
+    k, m, F, S = 10, 4, 1 << 20, 256
+    has_correct = hasattr(d, "ecamd_rs_correct")
+    lay = D.Layout.alloc(k + m, F, S)
+    saved = D.DeviceBuffer(lay.buf.nbytes)
+    words = D.DeviceBuffer(12 * S + 16)
+    checked = _lib.u32s([0])
+    host_counts = [_lib.C.c_int(0) for _ in range(4)]
+    args = (lay.buf.ptr, lay.stripe_stride, lay.frag_stride, F, S)
+    w = (words.ptr, words.ptr + 4 * S, words.ptr + 8 * S)
+
+    def pairs():
+        _lib.check(d.ecamd_rs_locate_pairs(k, m, None, *args, *w, checked, st.handle), "rs_locate_pairs")
+
+    def correct(counts=False):
+        _lib.check(d.ecamd_rs_correct(k, m, None, *args, *w, words.ptr + 12 * S if counts else None, checked, st.handle),
+                   "rs_correct")
+
+    def scrub():
+        _lib.check(d.ecamd_rs_scrub_pairs(k, m, *args, *w, *[_lib.C.byref(c) for c in host_counts], st.handle), "rs_scrub_pairs")
+
+    def fresh():
+        lay.fill_splitmix(nfrags=k, stream=st)
+        D.rs_encode(k, m, lay, stream=st)
+
+    def keep():
+        _lib.check(d.ecamd_memcpy_async(saved.ptr, lay.buf.ptr, lay.buf.nbytes, 2, st.handle), "keep")
+        st.synchronize()
+
+    def restore():
+        _lib.check(d.ecamd_memcpy_async(lay.buf.ptr, saved.ptr, lay.buf.nbytes, 2, st.handle), "restore")
+        st.synchronize()
+
+    def wall(fn):
+        """Mean ms of n calls, each on the restored damaged batch: clock around call plus synchronise."""
+        total = 0.0
+        for _ in range(n):
+            restore()
+            t0 = time.perf_counter()
+            fn()
+            st.synchronize()
+            total += time.perf_counter() - t0
+        return total * 1e3 / n
+
+    def repaired(what):
+        st.synchronize()
+        _lib.check(d.ecamd_rs_locate_pairs(k, m, None, *args, *w, checked, st.handle), "rs_locate_pairs")
+        st.synchronize()
+        assert not words.download(4 * S).any(), "%s must leave every stripe consistent" % what
+
+    d.ecamd_tune(b"bitslice", 2)
+    fresh()
+    (correct if has_correct else pairs)()
+    st.synchronize()
+    assert not words.download(12 * S).any(), "encoded stripes must read clean"
+    for _ in range(60):  # settle the clocks
+        pairs()
+    st.synchronize()
+    algo = S * (k + m) * F
+    ms = {}
+    for _ in range(reps):
+        ms.setdefault("pairs_clean", []).append(timed(st, pairs, n))
+        if has_correct:
+            ms.setdefault("correct_clean", []).append(timed(st, correct, n))
+            ms.setdefault("correct_counts_clean", []).append(timed(st, lambda: correct(True), n))
+    # (b) stripe 77: one word of fragment 2 and one of fragment 11
+    for f, at in ((2, 123456), (11, 987654)):
+        pos = 77 * lay.stripe_stride + f * lay.frag_stride + at
+        two = lay.buf.download(2, pos)
+        two[0] ^= 0x5A
+        two[1] ^= 0x01
+        lay.buf.upload(two, pos)
+    keep()
+    for suffix in ("one_dirty", "all_dirty"):
+        if suffix == "all_dirty":
+            # (c) fragments 3 and 12 of every stripe hold other data, so every word of every stripe needs the pair
+            fresh()
+            for f, seed in ((3, 0x5EED), (12, 0xBEEF)):
+                _lib.check(d.ecamd_fill_splitmix(lay.buf.ptr + f * lay.frag_stride, lay.stripe_stride, lay.frag_stride, 1, F,
+                                                 S, 0, seed, st.handle), "fill")
+            keep()
+        scrub()  # both paths once: results, and everything they allocate or compile outside the timing
+        repaired("scrub_pairs")
+        if has_correct:
+            restore()
+            correct(True)
+            st.synchronize()
+            got = words.download().view("uint32")
+            want = (S - 1, 0, 1, 0) if suffix == "one_dirty" else (0, 0, S, 0)
+            assert tuple(int(c) for c in got[3 * S:3 * S + 4]) == want, (suffix, got[3 * S:3 * S + 4])
+            repaired("correct")
+        for _ in range(reps):
+            ms.setdefault("scrub_pairs_" + suffix, []).append(wall(scrub))
+            if has_correct:
+                ms.setdefault("correct_" + suffix, []).append(wall(correct))
+    out = {"k": k, "m": m, "fragment_bytes": F, "stripes": S, "algorithmic_bytes": algo, "correct": has_correct,
+           "clean_timer": "HIP events around %d calls" % n,
+           "dirty_timer": "host wall clock around call plus stream synchronise, batch restored before each call"}
+    out.update({name: series(v, algo) for name, v in ms.items()})
+    if has_correct:
+        out["clean_correct_minus_pairs_ms"] = round(out["correct_clean"]["mean_ms"] - out["pairs_clean"]["mean_ms"], 4)
+        for suffix in ("one_dirty", "all_dirty"):
+            out["%s_scrub_over_correct" % suffix] = round(out["scrub_pairs_" + suffix]["mean_ms"] /
+                                                          out["correct_" + suffix]["mean_ms"], 3)
+    lay.buf.free()
+    saved.free()
+    words.free()
+    return out
+
+
 XOR_FORMS = (("generic", 0, 0), ("fused_4k", 1, 256), ("fused_1k", 1, 64), ("fused_default", 1, 0))
 
 
@@ -357,6 +480,11 @@ def main():
     ap.add_argument("--locate-only", action="store_true", help="with --pairs: time ecamd_rs_locate alone, as --tree PARENT does")
     ap.add_argument("--pairs-merge", default=None,
                     help="THIS,BEFORE,AFTER: --pairs documents of this commit and of two runs of the parent's tree")
+    ap.add_argument("--correct", action="store_true", help="measure ecamd_rs_correct at C3 instead")
+    ap.add_argument("--correct-merge", default=None,
+                    help="THIS,BEFORE,AFTER: --correct documents of this commit and of two runs of the parent's tree")
+    ap.add_argument("--added-launch-us", type=float, default=None,
+                    help="with --correct-merge: traced duration of the launches ecamd_rs_correct adds on a clean batch")
     ap.add_argument("--xor-shapes", default="10,6,4,1048576,256;3,3,3,4096,131072",
                     help="k,m,hd,fragment bytes,stripes; ...")
     ap.add_argument("--tree", default=None, help="run against the package and libraries of another built checkout")
@@ -388,6 +516,29 @@ def main():
             with open(a.out, "w") as f:
                 f.write(text + "\n")
         return
+    if a.correct_merge:
+        # the bar of (a): the parent's larger clean ecamd_rs_locate_pairs mean of the same session (run before
+        # and after this commit, --correct --tree PARENT), plus the spread between those two runs, plus the
+        # traced duration of the added launches
+        docs = []
+        for path in a.correct_merge.split(","):
+            with open(path) as f:
+                docs.append(json.load(f))
+        doc, before, after = docs
+        b, c = before["c3"]["pairs_clean"]["mean_ms"], after["c3"]["pairs_clean"]["mean_ms"]
+        added = (a.added_launch_us or 0.0) / 1e3
+        mean = doc["c3"]["correct_clean"]["mean_ms"]
+        bar = max(b, c) + abs(b - c) + added
+        doc["yardstick"] = {"parent_pairs_clean_ms": [b, c], "parent_spread_ms": round(abs(b - c), 4),
+                            "added_launch_ms": round(added, 4), "bar_ms": round(bar, 4), "correct_clean_mean_ms": mean,
+                            "within": bool(mean <= bar), "over_by_ms": round(max(0.0, mean - bar), 4),
+                            "parent_before": before["c3"], "parent_after": after["c3"]}
+        text = json.dumps(doc, indent=1)
+        print(text)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write(text + "\n")
+        return
     d = _lib.dev()
     st = D.Stream()
     per_cu = [int(x) for x in a.per_cu.split(",") if x.strip()]
@@ -396,6 +547,16 @@ def main():
         for shape in a.xor_shapes.split(";"):
             k, m, hd, F, S = (int(x) for x in shape.split(","))
             doc["shapes"].append(run_xor(d, st, k, m, hd, F, S, a.reps, a.n))
+        text = json.dumps(doc, indent=1)
+        print(text)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write(text + "\n")
+        return
+    if a.correct:
+        doc = {"tool": "tools/check_bench.py --correct", "reps": a.reps, "calls_per_rep": a.n,
+               "c3": run_correct(d, st, a.reps, a.n)}
+        d.ecamd_tune(b"bitslice", 1)
         text = json.dumps(doc, indent=1)
         print(text)
         if a.out:
