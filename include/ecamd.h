@@ -407,6 +407,52 @@ int ecamd_rs_correct(int k, int m, const int *missing, void *base, int64_t strip
 int ecamd_xor_correct(int k, int m, int hd, void *base, int64_t stripe_stride, int64_t frag_stride,
                       int64_t blocksize, int nstripes, uint32_t *d_status, uint32_t *d_suspects,
                       uint32_t *d_counts /* may be NULL */, void *stream);
+
+/* ---- flat_xor_hd with fragments missing: check, locate and correct what is left ----
+ * `missing` (-1 terminated, may be NULL) lists the lost fragments of every stripe of the batch; their
+ * slots are never read and never written, on any path.  The checks are the rows of
+ * ecamd_xor_check_plan_degraded (ecamd_host.h, where the reduction rule is stated): rows[p], the
+ * surviving row that parity p owns, and sig[f], the surviving rows that contain fragment f.  Per
+ * 16-bit word, S_p is the XOR of the stored fragments in rows[p].
+ *   check    d_status[s] gets bit k+p when S_p is non-zero anywhere in stripe s, surviving rows only.
+ *   locate   d_suspects[s] is 0 on a clean stripe, else the mask of covered fragments f such that in
+ *            every dirty word the set of non-zero rows is exactly sig[f] and those syndromes are equal.
+ *            Fragments that share a signature cannot be told apart and come back together (several
+ *            bits).  Missing fragments and available ones that no surviving row contains (sig[f] == 0)
+ *            never appear.  With one surviving row every fragment of that row is a suspect of a dirty
+ *            stripe; with none both words are 0.
+ *   correct  the locate, then on the same stream and with no host wait: a stripe with exactly one
+ *            suspect f gets S_q XORed into fragment f, q the lowest bit of sig[f]; only the non-zero
+ *            4-byte units are written, as ecamd_xor_correct does.  Every other stripe is not written.
+ *            d_counts as ecamd_xor_correct; the arrays keep what the locate found.
+ * *covered (host, may be NULL) is set to the mask of fragments with sig[f] != 0 -- the only ones whose
+ * damage these calls can see -- for an empty batch too.
+ * What can be told: with at most hd - 2 fragments missing every available fragment is covered; at
+ * hd 4 with one missing the signatures are still distinct, so one bad fragment is located and
+ * corrected; at hd 4 with two missing and at hd 3 with one missing some fragments share a signature and
+ * come back as a set, which correct leaves alone.  With nothing missing the words are those of
+ * ecamd_xor_check / ecamd_xor_locate / ecamd_xor_correct.
+ * Losing fragments lowers the distance: a stripe with one bad fragment more than the remaining checks
+ * can detect may read as a wrong single suspect and be "corrected" towards it, ending consistent -- the
+ * caveat of R == 2 at ecamd_rs_locate and of (3,3,3) at ecamd_xor_scrub.
+ * Whole tiles run the degraded form of the fused kernel (xor_check_kernel over slots: only the fragments of
+ * the surviving rows are loaded, so a (10,6,4) stripe with one lost issues 15 loads per lane, not 16);
+ * its launches count in ecamd_xor_check_fused_launches / ecamd_xor_locate_fused_launches.  Tails,
+ * fragments shorter than a tile, knob xor_check_fused 0 and stripes the 32-bit offsets cannot span go
+ * through the generic stage; the words are the same on every path.
+ * ECAMD_EINVAL, with the data, the arrays, d_counts and *covered untouched, for everything the plan
+ * rejects (a code init_xor_hd_code rejects, an index >= k+m, a repeated index, more than m entries),
+ * for the layout errors of ecamd_xor_check and, on locate and correct, for an odd blocksize. */
+int ecamd_xor_check_degraded(int k, int m, int hd, const int *missing, const void *base, int64_t stripe_stride,
+                             int64_t frag_stride, int64_t blocksize, int nstripes, uint32_t *d_status,
+                             uint32_t *covered, void *stream);
+int ecamd_xor_locate_degraded(int k, int m, int hd, const int *missing, const void *base, int64_t stripe_stride,
+                              int64_t frag_stride, int64_t blocksize, int nstripes, uint32_t *d_status,
+                              uint32_t *d_suspects, uint32_t *covered, void *stream);
+int ecamd_xor_correct_degraded(int k, int m, int hd, const int *missing, void *base, int64_t stripe_stride,
+                               int64_t frag_stride, int64_t blocksize, int nstripes, uint32_t *d_status,
+                               uint32_t *d_suspects, uint32_t *d_counts /* may be NULL */, uint32_t *covered,
+                               void *stream);
 /* Launches of correct_kernel enqueued by this process (one per call with a non-empty batch and at
  * least one checked fragment). */
 long long ecamd_correct_launches(void);

@@ -131,6 +131,28 @@ int ecamd_xor_code_tables(int k, int m, int hd, unsigned int *parity_bms, unsign
  * init_xor_hd_code accepts. */
 int ecamd_xor_check_plan(int k, int m, int hd, unsigned int *sig /* k+m */);
 
+/* The same plan for a stripe with fragments missing (ecamd_xor_check_degraded, ecamd_xor_locate_degraded,
+ * ecamd_xor_correct_degraded, ecamd.h).  The m check rows start as fragment masks h_p = parity bitmap p
+ * | 1 << (k+p) and are reduced by this rule, which callers may rely on:
+ *   - the missing fragments are taken in ascending index order, whatever the order of the list;
+ *   - for a missing fragment f the pivot is the lowest-index row still alive that has bit f;
+ *   - the pivot is XORed into every other live row that has bit f, and is then retired;
+ *   - if no live row has bit f, nothing happens.
+ * rows[p] is the reduced row p, or 0 if row p was retired.  A surviving row p contains the stored
+ * parity k+p and no missing fragment, so "row p" stays the check that parity p owns, with status bit
+ * k+p.  sig[f] is the mask of p with bit f in rows[p]: 0 for a missing fragment and for an available
+ * one that no surviving row contains.  *covered (may be NULL) is the mask of fragments with sig[f] != 0.
+ * With nothing missing (missing NULL or {-1}) rows[p] = h_p and sig is ecamd_xor_check_plan's.
+ * Signatures need not be distinct any more: fragments that share one cannot be told apart and are
+ * located together.  With at most hd - 2 missing every available fragment is covered; at hd 4 with one
+ * missing the signatures are still distinct.
+ * Returns the number of surviving rows (0 is possible), or -1 with every output untouched for a code
+ * init_xor_hd_code rejects, an index >= k+m, a repeated index, or more than m entries (`missing` ends
+ * at its first negative entry). */
+int ecamd_xor_check_plan_degraded(int k, int m, int hd, const int *missing /* -1 terminated, may be NULL */,
+                                  unsigned int *rows /* m */, unsigned int *sig /* k+m */,
+                                  unsigned int *covered /* may be NULL */);
+
 /* Exact plan of a reference operation on k+m buffers: op 0 = xor_code_encode, 1 = xor_hd_decode
  * (arg = decode_parity), 2 = xor_reconstruct_one (arg = index).  outputs[*nout] are the buffers
  * the reference modifies, sources[i] the bitmask of ORIGINAL buffers whose XOR output i ends up

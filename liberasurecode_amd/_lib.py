@@ -71,6 +71,8 @@ def host():
         _proto(h, "ecamd_split_tables", C.c_int,
                [IP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p])
         _proto(h, "ecamd_xor_check_plan", C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint)])
+        _proto(h, "ecamd_xor_check_plan_degraded", C.c_int,
+               [C.c_int, C.c_int, C.c_int, IP, C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(C.c_uint)])
         _host = h
     return _host
 
@@ -169,6 +171,12 @@ def dev():
                [C.c_int, C.c_int, IP, VP, C.c_int64, C.c_int64, C.c_int64, C.c_int, VP, VP, VP, VP, U32P, VP])
         _proto(d, "ecamd_xor_correct", C.c_int,
                [C.c_int, C.c_int, C.c_int, VP, C.c_int64, C.c_int64, C.c_int64, C.c_int, VP, VP, VP, VP])
+        _proto(d, "ecamd_xor_check_degraded", C.c_int,
+               [C.c_int, C.c_int, C.c_int, IP, VP, C.c_int64, C.c_int64, C.c_int64, C.c_int, VP, U32P, VP])
+        _proto(d, "ecamd_xor_locate_degraded", C.c_int,
+               [C.c_int, C.c_int, C.c_int, IP, VP, C.c_int64, C.c_int64, C.c_int64, C.c_int, VP, VP, U32P, VP])
+        _proto(d, "ecamd_xor_correct_degraded", C.c_int,
+               [C.c_int, C.c_int, C.c_int, IP, VP, C.c_int64, C.c_int64, C.c_int64, C.c_int, VP, VP, VP, U32P, VP])
         _proto(d, "ecamd_correct_launches", C.c_longlong, [])
         _proto(d, "ecamd_locate_fused_launches", C.c_longlong, [])
         _proto(d, "ecamd_xor_check_fused_launches", C.c_longlong, [])

@@ -28,6 +28,11 @@
 // correct_kernel reads the three words of each stripe and XORs the error values of a located fragment
 // or pair into the stored words -- on the same stream, with no host wait (DESIGN.md "Correct on the
 // device").
+//
+// Flat XOR with fragments missing (ecamd_xor_check_degraded, ecamd_xor_locate_degraded,
+// ecamd_xor_correct_degraded): the rows of ecamd_xor_check_plan_degraded through the same stages -- the
+// fused kernel over the participants alone (XorCheckSlotArgs), the generic stage and correct_kernel over
+// a CheckPlan of the reduced rows (DESIGN.md "Degraded flat XOR stripes").
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -36,6 +41,7 @@
 #include <map>
 #include <memory>
 #include <mutex>
+#include <type_traits>
 #include <vector>
 
 #include "../host/gf16.hpp"
@@ -627,6 +633,14 @@ struct XorCheckArgs {
     uint32_t masks[kXorCheckMaxRows];  // row p: parity bitmap p | 1 << (k + p), the stored parity folded in
     uint32_t sig[kXorCheckMaxFrags];   // ecamd_xor_check_plan
 };
+// The degraded form (ecamd_xor_check_degraded and its kin): the same fields over SLOTS, the available
+// fragments that occur in a surviving row of ecamd_xor_check_plan_degraded, ascending -- nfrags of them,
+// off32 / sig per slot, masks over slot numbers, sig over the nrows surviving rows packed densely -- and
+// the two tables that turn a slot and a packed row back into result bits.  k is unused.
+struct XorCheckSlotArgs : XorCheckArgs {
+    uint8_t slot_frag[kXorCheckMaxFrags];  // fragment index of slot i: its suspect bit
+    uint8_t row_bit[kXorCheckMaxRows];     // status bit of packed row r: k + the parity that owns it
+};
 
 // The check (LOCATE false) and locate form of flat XOR over whole tiles, one workgroup per tile of
 // blockDim.x * 16 bytes; grid = tiles_per_stripe * stripes.  The input side of xor_stream_kernel: one
@@ -643,9 +657,13 @@ struct XorCheckArgs {
 // equal" is "the 16-byte rows of sig[f] are equal and every other row is zero".  keep is ANDed across
 // the wave; one lane issues one atomicOr and one atomicAnd (relaxed, agent scope), as
 // locate_compare_kernel ends.
-template <int KG, bool LOCATE>
-__global__ void __launch_bounds__(256) xor_check_kernel(const XorCheckArgs a)
+// With Args = XorCheckSlotArgs this is the degraded form: the same tile over the slots, so KG comes from
+// the participant count -- a lost fragment, and an available one that no surviving row contains, is
+// never loaded -- and a row's status bit and a slot's suspect bit come from the two tables.
+template <int KG, bool LOCATE, class Args>
+__global__ void __launch_bounds__(256) xor_check_kernel(const Args a)
 {
+    constexpr bool SLOTS = std::is_same_v<Args, XorCheckSlotArgs>;
     typedef unsigned int v4 __attribute__((ext_vector_type(4)));
     const uint32_t t = blockIdx.x;
     const uint32_t s = t / a.tiles_per_stripe;
@@ -682,7 +700,11 @@ __global__ void __launch_bounds__(256) xor_check_kernel(const XorCheckArgs a)
         if (r >= a.nrows) break;
         const bool dirty = (syn[r][0] | syn[r][1] | syn[r][2] | syn[r][3]) != 0u;
         if (dirty) nz |= 1u << r;
-        if (__ballot(dirty) != 0ull) bits |= 1u << (a.k + r);
+        if constexpr (SLOTS) {
+            if (__ballot(dirty) != 0ull) bits |= 1u << a.row_bit[r];
+        } else {
+            if (__ballot(dirty) != 0ull) bits |= 1u << (a.k + r);
+        }
     }
     if (bits == 0u) return;
     if constexpr (!LOCATE) {
@@ -705,7 +727,12 @@ __global__ void __launch_bounds__(256) xor_check_kernel(const XorCheckArgs a)
             keep = 0u;
             if (equal)
                 for (int f = 0; f < a.nfrags; f++)
-                    if (a.sig[f] == nz) keep |= 1u << f;
+                    if (a.sig[f] == nz) {
+                        if constexpr (SLOTS)
+                            keep |= 1u << a.slot_frag[f];
+                        else
+                            keep |= 1u << f;
+                    }
         }
         for (int o = 32; o; o >>= 1) keep &= __shfl_xor(keep, o);
         if ((threadIdx.x & 63u) == 0u) {
@@ -717,16 +744,23 @@ __global__ void __launch_bounds__(256) xor_check_kernel(const XorCheckArgs a)
 
 std::atomic<long long> g_xor_check_fused{0}, g_xor_locate_fused{0};
 
-template <bool LOCATE>
-void xor_check_launch(int groups, dim3 grid, dim3 block, hipStream_t st, const XorCheckArgs& a)
+template <bool LOCATE, class Args>
+void xor_check_launch(int groups, dim3 grid, dim3 block, hipStream_t st, const Args& a)
 {
-    switch (groups) {  // 2 ((3,3,3): 6 fragments) to 7 ((20,6,4): 26)
-    case 2: hipLaunchKernelGGL((xor_check_kernel<2, LOCATE>), grid, block, 0, st, a); break;
-    case 3: hipLaunchKernelGGL((xor_check_kernel<3, LOCATE>), grid, block, 0, st, a); break;
-    case 4: hipLaunchKernelGGL((xor_check_kernel<4, LOCATE>), grid, block, 0, st, a); break;
-    case 5: hipLaunchKernelGGL((xor_check_kernel<5, LOCATE>), grid, block, 0, st, a); break;
-    case 6: hipLaunchKernelGGL((xor_check_kernel<6, LOCATE>), grid, block, 0, st, a); break;
-    default: hipLaunchKernelGGL((xor_check_kernel<7, LOCATE>), grid, block, 0, st, a); break;
+    // full stripes: 2 ((3,3,3): 6 fragments) to 7 ((20,6,4): 26); degraded: 1 (up to 4 participants) to 7
+    switch (groups) {
+    case 1:
+        if constexpr (std::is_same_v<Args, XorCheckSlotArgs>) {
+            hipLaunchKernelGGL((xor_check_kernel<1, LOCATE, Args>), grid, block, 0, st, a);
+            break;
+        }
+        [[fallthrough]];
+    case 2: hipLaunchKernelGGL((xor_check_kernel<2, LOCATE, Args>), grid, block, 0, st, a); break;
+    case 3: hipLaunchKernelGGL((xor_check_kernel<3, LOCATE, Args>), grid, block, 0, st, a); break;
+    case 4: hipLaunchKernelGGL((xor_check_kernel<4, LOCATE, Args>), grid, block, 0, st, a); break;
+    case 5: hipLaunchKernelGGL((xor_check_kernel<5, LOCATE, Args>), grid, block, 0, st, a); break;
+    case 6: hipLaunchKernelGGL((xor_check_kernel<6, LOCATE, Args>), grid, block, 0, st, a); break;
+    default: hipLaunchKernelGGL((xor_check_kernel<7, LOCATE, Args>), grid, block, 0, st, a); break;
     }
 }
 
@@ -740,18 +774,20 @@ void xor_check_launch(int groups, dim3 grid, dim3 block, hipStream_t st, const X
 // against 0.486 ms; tools/check_bench.py --xor, profiles/xor_check.json).  Returns
 // the bytes of each fragment covered, or 0 with nothing launched when it declines: knob
 // xor_check_fused 0, a fragment shorter than a tile, a stripe the 32-bit buffer offsets cannot span.
-int64_t xor_check_fused(int dev, int k, int m, const uint32_t* masks, const uint32_t* sig, const uint8_t* base,
-                        int64_t stripe_stride, int64_t frag_stride, int64_t blocksize, int nstripes, uint32_t* d_status,
-                        uint32_t* d_suspects, void* stream)
+// xor_check_tiles is the part both argument forms share: `a` comes with its tables filled, `last` is the
+// highest fragment index it loads.
+template <class Args>
+int64_t xor_check_tiles(int dev, Args& a, int last, const uint8_t* base, int64_t stripe_stride, int64_t frag_stride,
+                        int64_t blocksize, int nstripes, uint32_t* d_status, uint32_t* d_suspects, void* stream)
 {
-    const int n = k + m;
-    if (!g_tune.xor_check_fused || n <= 4 || n > kXorCheckMaxFrags || m > kXorCheckMaxRows || nstripes <= 0) return 0;
+    constexpr bool kSlots = std::is_same_v<Args, XorCheckSlotArgs>;
+    if (!g_tune.xor_check_fused || nstripes <= 0) return 0;
     const int knob_threads = g_tune.xor_check_threads;
     const int threads = knob_threads ? knob_threads : 64;
     const int64_t tile = static_cast<int64_t>(threads) * 16;
     const int64_t cover = blocksize / tile * tile;
     if (cover == 0 || stripe_stride < 0) return 0;
-    if ((n - 1) * frag_stride + blocksize >= (int64_t(1) << 31)) return 0;
+    if (last * frag_stride + blocksize >= (int64_t(1) << 31)) return 0;
     const uint64_t tps = static_cast<uint64_t>(cover / tile);
     const int wgs_knob = g_tune.xor_wgs;
     const int wgs = wgs_knob > 0 ? wgs_knob : 3;
@@ -759,18 +795,15 @@ int64_t xor_check_fused(int dev, int k, int m, const uint32_t* masks, const uint
     const uint64_t limit = static_cast<uint64_t>(std::max<int>(g_tune.xor_tiles_per_slot, 0)) * static_cast<uint64_t>(256 / threads);
     const int per = launch_stripes(nstripes, tps, slots, limit);
     if (tps * static_cast<uint64_t>(per) > 0x7fffffffull) return 0;
-    XorCheckArgs a{};
     a.stripe_stride = stripe_stride;
-    a.records = static_cast<uint32_t>((n - 1) * frag_stride + cover);
+    a.records = static_cast<uint32_t>(last * frag_stride + cover);
     a.tiles_per_stripe = static_cast<uint32_t>(tps);
-    a.nfrags = n;
-    a.nrows = m;
-    a.k = k;
-    for (int f = 0; f < n; f++) {
-        a.off32[f] = static_cast<int32_t>(f * frag_stride);
-        a.sig[f] = sig[f];
+    for (int i = 0; i < a.nfrags; i++) {
+        int f = i;
+        if constexpr (kSlots) f = a.slot_frag[i];
+        a.off32[i] = static_cast<int32_t>(f * frag_stride);
     }
-    for (int p = 0; p < m; p++) a.masks[p] = masks[p] | (1u << (k + p));
+    const int groups = (a.nfrags + 3) / 4;
     const auto st = static_cast<hipStream_t>(stream);
     for (int s0 = 0; s0 < nstripes; s0 += per) {
         const int ns = std::min(per, nstripes - s0);
@@ -779,13 +812,60 @@ int64_t xor_check_fused(int dev, int k, int m, const uint32_t* masks, const uint
         a.suspects = d_suspects ? d_suspects + s0 : nullptr;
         const dim3 grid(static_cast<unsigned>(tps * static_cast<uint64_t>(ns))), block(static_cast<unsigned>(threads));
         if (d_suspects)
-            xor_check_launch<true>((n + 3) / 4, grid, block, st, a);
+            xor_check_launch<true>(groups, grid, block, st, a);
         else
-            xor_check_launch<false>((n + 3) / 4, grid, block, st, a);
+            xor_check_launch<false>(groups, grid, block, st, a);
         HIP_TRY(hipGetLastError());
         (d_suspects ? g_xor_locate_fused : g_xor_check_fused).fetch_add(1, std::memory_order_relaxed);
     }
     return cover;
+}
+
+int64_t xor_check_fused(int dev, int k, int m, const uint32_t* masks, const uint32_t* sig, const uint8_t* base,
+                        int64_t stripe_stride, int64_t frag_stride, int64_t blocksize, int nstripes, uint32_t* d_status,
+                        uint32_t* d_suspects, void* stream)
+{
+    const int n = k + m;
+    if (n <= 4 || n > kXorCheckMaxFrags || m > kXorCheckMaxRows) return 0;
+    XorCheckArgs a{};
+    a.nfrags = n;
+    a.nrows = m;
+    a.k = k;
+    for (int f = 0; f < n; f++) a.sig[f] = sig[f];
+    for (int p = 0; p < m; p++) a.masks[p] = masks[p] | (1u << (k + p));
+    return xor_check_tiles(dev, a, n - 1, base, stripe_stride, frag_stride, blocksize, nstripes, d_status, d_suspects, stream);
+}
+
+// The slots of a degraded flat XOR plan (ecamd_xor_check_plan_degraded), what the degraded form of xor_check_kernel
+// works on: the participants -- the available fragments that occur in a surviving row, ascending --
+// and the surviving rows packed densely in the order of their owners.
+struct XorSlots {
+    std::vector<int> frag;        // fragment index of slot i
+    std::vector<uint32_t> masks;  // packed row r over slot numbers
+    std::vector<uint32_t> sig;    // slot i over packed rows
+    std::vector<int> row_bit;     // status bit of packed row r: k + its owner
+};
+
+// The same stage for a degraded stripe: only the participants are loaded, in (participants + 3) / 4
+// groups.  Declines as xor_check_fused does, and for a plan without a surviving row.
+int64_t xor_check_fused_slots(int dev, const XorSlots& sl, const uint8_t* base, int64_t stripe_stride, int64_t frag_stride,
+                              int64_t blocksize, int nstripes, uint32_t* d_status, uint32_t* d_suspects, void* stream)
+{
+    const int n = static_cast<int>(sl.frag.size()), rows = static_cast<int>(sl.masks.size());
+    if (n < 1 || n > kXorCheckMaxFrags || rows < 1 || rows > kXorCheckMaxRows) return 0;
+    XorCheckSlotArgs a{};
+    a.nfrags = n;
+    a.nrows = rows;
+    for (int i = 0; i < n; i++) {
+        a.sig[i] = sl.sig[static_cast<size_t>(i)];
+        a.slot_frag[i] = static_cast<uint8_t>(sl.frag[static_cast<size_t>(i)]);
+    }
+    for (int r = 0; r < rows; r++) {
+        a.masks[r] = sl.masks[static_cast<size_t>(r)];
+        a.row_bit[r] = static_cast<uint8_t>(sl.row_bit[static_cast<size_t>(r)]);
+    }
+    return xor_check_tiles(dev, a, sl.frag.back(), base, stripe_stride, frag_stride, blocksize, nstripes, d_status, d_suspects,
+                           stream);
 }
 
 // What the entry points differ in.  Fragment f of stripe s lies at base + s*stripe_stride +
@@ -801,6 +881,10 @@ struct CheckPlan {
     PairsTable pairs;                //   and its pair table (ecamd_rs_locate_pairs)
     CorrectTable correct;            // the correction table (ecamd_rs_correct: with the cached map; flat XOR: xor_correct_table)
     std::vector<int> bitmaps;        // or the parity bitmaps as 0 / 1 (flat XOR)
+    // flat XOR with fragments missing (xor_degraded_call): masks and bitmaps are the reduced rows over
+    // `inputs`, sig stays empty and whole tiles take xor_check_fused_slots over these
+    bool degraded = false;
+    XorSlots slots;
 };
 
 // Bytes [from, bs) of the checked fragments at off[] (bit bits[r] each) of every stripe against what
@@ -960,6 +1044,10 @@ int run_check(int dev, const CheckPlan& p, const void* base, int64_t stripe_stri
         // flat XOR: one launch reads all K + R fragments of a tile and takes the syndromes from the loads
         cover = xor_check_fused(dev, K, R, p.masks.data(), p.sig.data(), b, stripe_stride, frag_stride, blocksize, nstripes,
                                 d_status, locating ? d_suspects : nullptr, stream);
+    } else if (p.degraded) {
+        // the same over the participants of the reduced rows alone
+        cover = xor_check_fused_slots(dev, p.slots, b, stripe_stride, frag_stride, blocksize, nstripes, d_status,
+                                      locating ? d_suspects : nullptr, stream);
     }
     if (cover < 0) return static_cast<int>(cover);
     LocateCmpArgs loc{};
@@ -1014,20 +1102,38 @@ int rs_call(bool locate, int k, int m, const int* missing, const void* base, int
 
 // The correction table of a flat XOR code (CorrectTable, ecamd_internal.hpp) from its check plan:
 // fragment f is participant f, its pivot the lowest row of sig[f], every scale 1.  Device memory made
-// at the first call that asks, per (device, k, m, hd), and kept for the life of the process (a few
-// accepted codes, 128 bytes each).
-int xor_correct_table(int dev, int k, int m, int hd, const std::vector<uint32_t>& sig, CorrectTable& out)
+// at the first call that asks, per (device, k, m, hd, mask of lost fragments), and kept for the life of
+// the process (a few accepted codes and the loss patterns a caller meets, 128 bytes each).  With
+// fragments lost (`plan` degraded) fragment f is the participant correct_kernel loads in its place --
+// its index among plan.inputs, or K + r for the owner of packed row r -- and its pivot the packed row
+// of the lowest bit of sig[f]; a fragment no surviving row contains takes no part.
+int xor_correct_table(int dev, int k, int m, int hd, uint32_t lost, const std::vector<uint32_t>& sig, const CheckPlan& plan,
+                      CorrectTable& out)
 {
     static std::mutex mu;
-    static std::map<std::array<int, 4>, const uint32_t*> tables;
+    static std::map<std::array<int, 5>, const uint32_t*> tables;
     const std::lock_guard<std::mutex> lk(mu);
-    const uint32_t*& slot = tables[{dev, k, m, hd}];
+    const uint32_t*& slot = tables[{dev, k, m, hd, static_cast<int>(lost)}];
     if (!slot) {
         uint32_t tab[32];
         for (int f = 0; f < 32; f++)
             tab[f] = f < k + m && sig[static_cast<size_t>(f)]
                          ? static_cast<uint32_t>(f) | static_cast<uint32_t>(__builtin_ctz(sig[static_cast<size_t>(f)])) << 8 | 1u << 16
                          : 0xffffffffu;
+        if (plan.degraded) {
+            const int K = static_cast<int>(plan.inputs.size()), R = static_cast<int>(plan.checked.size());
+            for (int f = 0; f < k + m; f++) {
+                if (tab[f] == 0xffffffffu) continue;
+                int part = -1, row = -1;
+                for (int j = 0; j < K; j++)
+                    if (plan.inputs[static_cast<size_t>(j)] == f) part = j;
+                for (int r = 0; r < R; r++) {
+                    if (plan.checked[static_cast<size_t>(r)] == f) part = K + r;
+                    if (row < 0 && plan.checked[static_cast<size_t>(r)] == k + __builtin_ctz(sig[static_cast<size_t>(f)])) row = r;
+                }
+                tab[f] = part < 0 || row < 0 ? 0xffffffffu : static_cast<uint32_t>(part) | static_cast<uint32_t>(row) << 8 | 1u << 16;
+            }
+        }
         void* d = nullptr;
         HIP_TRY(hipMalloc(&d, sizeof(tab)));
         const hipError_t err = hipMemcpy(d, tab, sizeof(tab), hipMemcpyHostToDevice);  // once per code, before anything is enqueued
@@ -1064,7 +1170,64 @@ int xor_call(bool locate, int k, int m, int hd, const void* base, int64_t stripe
         for (int j = 0; j < k; j++) p.bitmaps.push_back((pb[r] >> j) & 1u);
     }
     p.A = &p.bitmaps;
-    if (fix_base && (rc = xor_correct_table(dev, k, m, hd, p.sig, p.correct))) return rc;
+    if (fix_base && (rc = xor_correct_table(dev, k, m, hd, 0u, p.sig, p, p.correct))) return rc;
+    return run_check(dev, p, base, stripe_stride, frag_stride, blocksize, nstripes, d_status, locate ? d_suspects : nullptr,
+                     stream, nullptr, fix_base, d_counts);
+}
+
+// ecamd_xor_check_degraded (locate false), ecamd_xor_locate_degraded and ecamd_xor_correct_degraded: the
+// rows of ecamd_xor_check_plan_degraded as a check plan.  The owner parity of each surviving row is
+// checked, every other participant -- the parities of retired pivot rows among them -- is an input, and
+// the map is the reduced rows over those inputs; a fragment that is lost, or that no surviving row
+// contains, is in neither list, so no stage reads or writes its slot.
+int xor_degraded_call(bool locate, int k, int m, int hd, const int* missing, const void* base, int64_t stripe_stride,
+                      int64_t frag_stride, int64_t blocksize, int nstripes, uint32_t* d_status, uint32_t* d_suspects,
+                      uint32_t* covered, void* stream, void* fix_base = nullptr, uint32_t* d_counts = nullptr)
+{
+    int dev = 0;
+    int rc = dev_ensure(&dev);
+    if (rc) return rc;
+    unsigned rows[32], sig[32], cov = 0;
+    if (k <= 0 || m <= 0 || k + m > 32 || ecamd_xor_check_plan_degraded(k, m, hd, missing, rows, sig, &cov) < 0)
+        return dev_fail(ECAMD_EINVAL, "not a flat_xor_hd code (k=%d m=%d hd=%d) or a bad list of missing fragments", k, m, hd);
+    if ((rc = check_layout(locate, base, stripe_stride, frag_stride, blocksize, nstripes, d_status, d_suspects))) return rc;
+    uint32_t lost = 0;
+    if (missing)
+        for (int i = 0; missing[i] > -1; i++) lost |= 1u << missing[i];
+    CheckPlan p;
+    p.degraded = true;
+    for (int r = 0; r < m; r++)
+        if (rows[r]) p.checked.push_back(k + r);
+    for (int f = 0; f < k + m; f++) {
+        if (!sig[f]) continue;
+        p.slots.frag.push_back(f);
+        if (!(f >= k && rows[f - k])) p.inputs.push_back(f);
+    }
+    const int K = static_cast<int>(p.inputs.size()), N = static_cast<int>(p.slots.frag.size());
+    for (int f : p.checked) {
+        const unsigned row = rows[f - k];
+        uint32_t over_inputs = 0, over_slots = 0;
+        for (int j = 0; j < K; j++) {
+            const unsigned bit = (row >> p.inputs[static_cast<size_t>(j)]) & 1u;
+            over_inputs |= bit << j;
+            p.bitmaps.push_back(static_cast<int>(bit));
+        }
+        for (int i = 0; i < N; i++) over_slots |= ((row >> p.slots.frag[static_cast<size_t>(i)]) & 1u) << i;
+        p.masks.push_back(over_inputs);
+        p.slots.masks.push_back(over_slots);
+        p.slots.row_bit.push_back(f);
+    }
+    for (int i = 0; i < N; i++) {
+        const unsigned over_owners = sig[p.slots.frag[static_cast<size_t>(i)]];
+        uint32_t packed = 0;  // the same over the surviving rows in their packed order
+        for (size_t r = 0; r < p.checked.size(); r++) packed |= ((over_owners >> (p.checked[r] - k)) & 1u) << r;
+        p.slots.sig.push_back(packed);
+    }
+    p.A = &p.bitmaps;
+    if (fix_base && !p.checked.empty() &&
+        (rc = xor_correct_table(dev, k, m, hd, lost, std::vector<uint32_t>(sig, sig + k + m), p, p.correct)))
+        return rc;
+    if (covered) *covered = cov;  // for an empty batch too
     return run_check(dev, p, base, stripe_stride, frag_stride, blocksize, nstripes, d_status, locate ? d_suspects : nullptr,
                      stream, nullptr, fix_base, d_counts);
 }
@@ -1245,6 +1408,30 @@ int ecamd_xor_correct(int k, int m, int hd, void* base, int64_t stripe_stride, i
 {
     return xor_call(true, k, m, hd, base, stripe_stride, frag_stride, blocksize, nstripes, d_status, d_suspects, stream, base,
                     d_counts);
+}
+
+int ecamd_xor_check_degraded(int k, int m, int hd, const int* missing, const void* base, int64_t stripe_stride,
+                             int64_t frag_stride, int64_t blocksize, int nstripes, uint32_t* d_status, uint32_t* covered,
+                             void* stream)
+{
+    return xor_degraded_call(false, k, m, hd, missing, base, stripe_stride, frag_stride, blocksize, nstripes, d_status, nullptr,
+                             covered, stream);
+}
+
+int ecamd_xor_locate_degraded(int k, int m, int hd, const int* missing, const void* base, int64_t stripe_stride,
+                              int64_t frag_stride, int64_t blocksize, int nstripes, uint32_t* d_status, uint32_t* d_suspects,
+                              uint32_t* covered, void* stream)
+{
+    return xor_degraded_call(true, k, m, hd, missing, base, stripe_stride, frag_stride, blocksize, nstripes, d_status,
+                             d_suspects, covered, stream);
+}
+
+int ecamd_xor_correct_degraded(int k, int m, int hd, const int* missing, void* base, int64_t stripe_stride,
+                               int64_t frag_stride, int64_t blocksize, int nstripes, uint32_t* d_status, uint32_t* d_suspects,
+                               uint32_t* d_counts, uint32_t* covered, void* stream)
+{
+    return xor_degraded_call(true, k, m, hd, missing, base, stripe_stride, frag_stride, blocksize, nstripes, d_status,
+                             d_suspects, covered, stream, base, d_counts);
 }
 
 long long ecamd_correct_launches(void) { return g_correct_launches.load(std::memory_order_relaxed); }

@@ -198,6 +198,47 @@ int ecamd_xor_check_plan(int k, int m, int hd, unsigned int* sig)
     return 0;
 }
 
+int ecamd_xor_check_plan_degraded(int k, int m, int hd, const int* missing, unsigned int* rows, unsigned int* sig,
+                                  unsigned int* covered)
+{
+    XorCode c;
+    if (!rows || !sig || !xor_code_lookup(k, m, hd, c)) return -1;
+    const int n = k + m;
+    unsigned int lost = 0;
+    if (missing)
+        for (int i = 0; missing[i] > -1; i++) {
+            const int f = missing[i];
+            if (i >= m || f >= n || ((lost >> f) & 1u)) return -1;
+            lost |= 1u << f;
+        }
+    unsigned int h[32], live = (1u << m) - 1u;
+    for (int p = 0; p < m; p++) h[p] = c.parity_bms[p] | 1u << (k + p);
+    for (int f = 0; f < n; f++) {  // ascending, whatever the order of the list
+        if (!((lost >> f) & 1u)) continue;
+        int pv = -1;
+        for (int p = 0; p < m && pv < 0; p++)
+            if (((live >> p) & 1u) && ((h[p] >> f) & 1u)) pv = p;
+        if (pv < 0) continue;
+        for (int p = 0; p < m; p++)
+            if (p != pv && ((live >> p) & 1u) && ((h[p] >> f) & 1u)) h[p] ^= h[pv];
+        live &= ~(1u << pv);
+    }
+    int alive = 0;
+    for (int p = 0; p < m; p++) {
+        rows[p] = ((live >> p) & 1u) ? h[p] : 0u;
+        alive += static_cast<int>((live >> p) & 1u);
+    }
+    unsigned int cov = 0;
+    for (int f = 0; f < n; f++) {
+        sig[f] = 0;
+        for (int p = 0; p < m; p++)
+            if ((rows[p] >> f) & 1u) sig[f] |= 1u << p;
+        if (sig[f]) cov |= 1u << f;
+    }
+    if (covered) *covered = cov;
+    return alive;
+}
+
 int ecamd_xor_plan(int op, int k, int m, int hd, const unsigned int* parity_bms,
                    const unsigned int* data_bms, const int* missing, int arg, int* outputs,
                    uint64_t* sources, int* nout)

@@ -176,9 +176,18 @@ def rs_check(k, m, lay: Layout, missing=(), stream=None):
     return status, checked.value
 
 
-def xor_check(k, m, hd, lay: Layout, stream=None):
+def xor_check(k, m, hd, lay: Layout, stream=None, missing=()):
     """ecamd_xor_check: status[s] has bit k + p set when stored parity p of stripe s differs from the
-    XOR its parity bitmap names."""
+    XOR its parity bitmap names.  With a non-empty `missing`, ecamd_xor_check_degraded: (status,
+    covered_mask) -- bit k + p for the surviving check row parity p owns (ecamd_xor_check_plan_degraded),
+    covered_mask the fragments some surviving row contains; missing slots are never read."""
+    missing = list(missing)
+    if missing:
+        covered = C.c_uint32(0)
+        status = _status(lambda d: dev().ecamd_xor_check_degraded(
+            k, m, hd, ints(missing + [-1]), lay.buf.ptr, lay.stripe_stride, lay.frag_stride, lay.blocksize,
+            lay.nstripes, d, C.byref(covered), _s(stream)), lay, stream, "xor_check_degraded")
+        return status, covered.value
     return _status(lambda d: dev().ecamd_xor_check(
         k, m, hd, lay.buf.ptr, lay.stripe_stride, lay.frag_stride, lay.blocksize, lay.nstripes, d,
         _s(stream)), lay, stream, "xor_check")
@@ -209,8 +218,17 @@ def rs_locate(k, m, lay: Layout, missing=(), stream=None):
     return status, suspects, checked.value
 
 
-def xor_locate(k, m, hd, lay: Layout, stream=None):
-    """ecamd_xor_locate: (status, suspects) of full flat_xor_hd stripes."""
+def xor_locate(k, m, hd, lay: Layout, stream=None, missing=()):
+    """ecamd_xor_locate: (status, suspects) of full flat_xor_hd stripes.  With a non-empty `missing`,
+    ecamd_xor_locate_degraded: (status, suspects, covered_mask); fragments that share a signature come
+    back together, several bits in one word."""
+    missing = list(missing)
+    if missing:
+        covered = C.c_uint32(0)
+        status, suspects = _status_suspects(lambda d, u: dev().ecamd_xor_locate_degraded(
+            k, m, hd, ints(missing + [-1]), lay.buf.ptr, lay.stripe_stride, lay.frag_stride, lay.blocksize,
+            lay.nstripes, d, u, C.byref(covered), _s(stream)), lay, stream, "xor_locate_degraded")
+        return status, suspects, covered.value
     return _status_suspects(lambda d, u: dev().ecamd_xor_locate(
         k, m, hd, lay.buf.ptr, lay.stripe_stride, lay.frag_stride, lay.blocksize, lay.nstripes, d, u,
         _s(stream)), lay, stream, "xor_locate")
@@ -300,8 +318,17 @@ def rs_correct(k, m, lay: Layout, missing=(), pairs=True, stream=None):
         lay.nstripes, d, u, p, c, None, _s(stream)), lay, stream, "rs_correct", pairs)
 
 
-def xor_correct(k, m, hd, lay: Layout, stream=None):
-    """ecamd_xor_correct on full flat_xor_hd stripes: (status, suspects, None, counts) as rs_correct."""
+def xor_correct(k, m, hd, lay: Layout, stream=None, missing=()):
+    """ecamd_xor_correct on full flat_xor_hd stripes: (status, suspects, None, counts) as rs_correct.
+    With a non-empty `missing`, ecamd_xor_correct_degraded: (status, suspects, None, counts,
+    covered_mask); only a stripe with exactly one suspect is written, never a missing slot."""
+    missing = list(missing)
+    if missing:
+        covered = C.c_uint32(0)
+        out = _correct(lambda d, u, p, c: dev().ecamd_xor_correct_degraded(
+            k, m, hd, ints(missing + [-1]), lay.buf.ptr, lay.stripe_stride, lay.frag_stride, lay.blocksize,
+            lay.nstripes, d, u, c, C.byref(covered), _s(stream)), lay, stream, "xor_correct_degraded", False)
+        return out + (covered.value,)
     return _correct(lambda d, u, p, c: dev().ecamd_xor_correct(
         k, m, hd, lay.buf.ptr, lay.stripe_stride, lay.frag_stride, lay.blocksize, lay.nstripes, d, u, c,
         _s(stream)), lay, stream, "xor_correct", False)

@@ -24,7 +24,10 @@ kernel existed) and (c) each tile form of the fused kernel (knob xor_check_threa
 default), on clean data and then on an all-dirty batch (data fragment 1 of every stripe rewritten).
 The bar for (c) on clean data is (a)'s mean plus the spread of (a)'s own repetitions.  `--tree DIR` runs
 the tool against the package and built libraries of another checkout: with the parent commit's, `--xor`
-gives (a) and (b) as that commit runs them (it has the generic path alone).
+gives (a) and (b) as that commit runs them (it has the generic path alone).  `--xor --missing LIST`
+measures the degraded calls instead, on the first shape, clean data and default knobs: ecamd_xor_check
+against ecamd_xor_check_degraded with LIST lost (and the two locates), alternating; the bar for the
+degraded form is the full-stripe mean plus the larger spread of the two series.
 
 `--pairs` measures ecamd_rs_locate_pairs (C3 only) against ecamd_rs_locate, alternating: (a) on a clean
 batch -- the pair stage adds one memset, one launch whose workgroups all end after two loads, and one
@@ -472,6 +475,56 @@ def run_xor(d, st, k, m, hd, F, S, reps, n):
     return out
 
 
+def run_xor_degraded(d, st, k, m, hd, F, S, missing, reps, n):
+    """One flat XOR shape on clean data, default knobs: ecamd_xor_check on the full stripes against
+    ecamd_xor_check_degraded with `missing` lost, alternating -- the same launches over one load group
+    slot fewer per lost or uncovered fragment -- and the same pair for the locate."""
+    lay = D.Layout.alloc(k + m, F, S)
+    lay.fill_splitmix(nfrags=k, stream=st)
+    words = D.DeviceBuffer(8 * S)
+    where = (lay.buf.ptr, lay.stripe_stride, lay.frag_stride, F, S)
+    lost = _lib.ints(list(missing) + [-1])
+    covered = _lib.C.c_uint32(0)
+    calls = {
+        "check_full": lambda: _lib.check(d.ecamd_xor_check(k, m, hd, *where, words.ptr, st.handle), "xor_check"),
+        "check_degraded": lambda: _lib.check(d.ecamd_xor_check_degraded(
+            k, m, hd, lost, *where, words.ptr, _lib.C.byref(covered), st.handle), "xor_check_degraded"),
+        "locate_full": lambda: _lib.check(d.ecamd_xor_locate(k, m, hd, *where, words.ptr, words.ptr + 4 * S, st.handle),
+                                          "xor_locate"),
+        "locate_degraded": lambda: _lib.check(d.ecamd_xor_locate_degraded(
+            k, m, hd, lost, *where, words.ptr, words.ptr + 4 * S, _lib.C.byref(covered), st.handle), "xor_locate_degraded"),
+    }
+    D.xor_encode(k, m, hd, lay, stream=st)
+    for name, call in calls.items():  # every path once: results, launch counters, scratch outside the timing
+        c0 = (d.ecamd_xor_check_fused_launches(), d.ecamd_xor_locate_fused_launches())
+        call()
+        st.synchronize()
+        c1 = (d.ecamd_xor_check_fused_launches(), d.ecamd_xor_locate_fused_launches())
+        assert (c1[0] > c0[0], c1[1] > c0[1]) == (name.startswith("check"), name.startswith("locate")), (name, c0, c1)
+        assert not words.download().any(), "encoded stripes must read clean (%s)" % name
+    for _ in range(60):  # settle the clocks
+        D.xor_encode(k, m, hd, lay, stream=st)
+    st.synchronize()
+    ms = {}
+    for _ in range(reps):
+        for name, call in calls.items():
+            ms.setdefault(name, []).append(timed(st, call, n))
+    participants = bin(covered.value).count("1")
+    out = {"k": k, "m": m, "hd": hd, "fragment_bytes": F, "stripes": S, "missing": list(missing),
+           "covered_mask": covered.value, "fragments_loaded_full": k + m, "fragments_loaded_degraded": participants,
+           "load_groups_full": (k + m + 3) // 4, "load_groups_degraded": (participants + 3) // 4}
+    out.update({name: series(v, S * (k + m if name.endswith("full") else participants) * F) for name, v in ms.items()})
+    for op in ("check", "locate"):
+        full, deg = out[op + "_full"], out[op + "_degraded"]
+        spread = max(full["spread_ms"], deg["spread_ms"])  # the run-to-run spread this run shows
+        out[op + "_spread_ms"] = spread
+        out[op + "_degraded_minus_full_ms"] = round(deg["mean_ms"] - full["mean_ms"], 4)
+        out[op + "_degraded_within_spread_of_full"] = bool(deg["mean_ms"] <= full["mean_ms"] + spread)
+    lay.buf.free()
+    words.free()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--locate", action="store_true", help="measure ecamd_rs_locate at C3 instead")
@@ -487,6 +540,9 @@ def main():
                     help="with --correct-merge: traced duration of the launches ecamd_rs_correct adds on a clean batch")
     ap.add_argument("--xor-shapes", default="10,6,4,1048576,256;3,3,3,4096,131072",
                     help="k,m,hd,fragment bytes,stripes; ...")
+    ap.add_argument("--missing", default=None,
+                    help="with --xor: comma-separated lost fragments; time ecamd_xor_check_degraded / _locate_degraded "
+                         "against the full-stripe calls on the first shape instead")
     ap.add_argument("--tree", default=None, help="run against the package and libraries of another built checkout")
     ap.add_argument("--parent-check-ms", type=float, default=None)
     ap.add_argument("--reps", type=int, default=5)
@@ -542,6 +598,17 @@ def main():
     d = _lib.dev()
     st = D.Stream()
     per_cu = [int(x) for x in a.per_cu.split(",") if x.strip()]
+    if a.xor and a.missing:
+        k, m, hd, F, S = (int(x) for x in a.xor_shapes.split(";")[0].split(","))
+        missing = [int(x) for x in a.missing.split(",")]
+        doc = {"tool": "tools/check_bench.py --xor --missing " + a.missing, "reps": a.reps, "calls_per_rep": a.n,
+               "shape": run_xor_degraded(d, st, k, m, hd, F, S, missing, a.reps, a.n)}
+        text = json.dumps(doc, indent=1)
+        print(text)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write(text + "\n")
+        return
     if a.xor:
         doc = {"tool": "tools/check_bench.py --xor", "fused_kernel": hasattr(d, "ecamd_xor_check_fused_launches"), "reps": a.reps, "calls_per_rep": a.n, "shapes": []}
         for shape in a.xor_shapes.split(";"):
