@@ -465,6 +465,51 @@ long long ecamd_xor_locate_fused_launches(void);
  * the bitsliced form declines, or a kernel that would need scratch), < 0 on error. */
 int ecamd_locate_prebuild(int k, int m, const int *missing, const char *arch, const char *dir);
 
+/* ---- decode from device masks: every stripe lost its own set of fragments, named on the device ----
+ * The erasure counterpart of ecamd_rs_correct (rs_vand only).  d_lost (nstripes uint32, DEVICE memory)
+ * holds one mask per stripe: bit f set when fragment f of stripe s is lost.  The word is read on the
+ * device, in stream order; it may have been written by earlier work on the same stream
+ * (ecamd_frame_status_masks below, a copy, a kernel of the caller's).  Per stripe, with L = d_lost[s]:
+ *   L == 0                          nothing of the stripe is read or written; d_result[s] = 0.
+ *   a bit >= k+m, or more than m    not recoverable: nothing of the stripe is written;
+ *   bits                            d_result[s] = 0x80000000 | popcount(L).
+ *   otherwise                       the inputs are the first k fragments not in L (ecamd_rs_decode's rule);
+ *                                   the outputs are the lost data fragments, ascending, then -- with
+ *                                   rebuild_parity -- the lost parity fragments, ascending.  The bytes
+ *                                   written are exactly those ecamd_rs_decode_multi writes for the
+ *                                   ascending list of L; d_result[s] = the number of fragments written.
+ * Lost slots that are not rebuilt (lost parity without rebuild_parity, every slot of an unrecoverable
+ * stripe) are never written, surviving fragments are never written, bytes between blocksize and
+ * frag_stride are never written, and lost slots are never read: they may hold anything.
+ * d_result (nstripes uint32, device memory, may be NULL).  d_counts (3 uint32, device memory, may be
+ * NULL) is overwritten with the number of stripes left alone (result 0), rebuilt, and unrecoverable.
+ * There is no host dependence inside the call: no stream synchronise, no copy to the host, no launch
+ * whose shape depends on the masks, no map-cache entry, no bitsliced launch and no compile -- RS(20,8)
+ * has 4.4 million patterns and each costs what any other costs.  The launches are fixed: a plan
+ * kernel (one wave per stripe works out the stripe's coefficients from the code's generator by
+ * Gauss-Jordan in shift-and-xor arithmetic: ecamd_masks_plan.hpp, the same text the host test checks
+ * against ecamd_rs_decode_map), the data kernel (per stripe: nibble tables built in LDS from the
+ * stripe's coefficients, 128-bit loads of the k inputs, 128-bit stores of the outputs; a stripe with
+ * nothing to write costs one word load per workgroup that visits it; tiles of 4096 bytes, the last
+ * partial 16-byte chunk byte-exact), and with d_counts a one-workgroup count.  The per-stripe plans
+ * live in library-owned scratch per (device, stream), 560 bytes per stripe, which grows only when a
+ * larger batch arrives (growing waits for the stream once, as the check's scratch does).  The first
+ * call for a (k, m) on a device uploads that code's generator, once.
+ * ECAMD_EINVAL, with the data and the arrays untouched, for a null d_lost or base, the layout errors
+ * of the other strided calls (16-byte aligned base and strides, frag_stride >= blocksize >= 1),
+ * k+m > 32, m > 8, and an ODD blocksize (as ecamd_rs_locate and ecamd_rs_correct; the frontend and
+ * ecamd_frame_geometry only produce even sizes).  nstripes == 0 returns 0 and writes nothing.
+ * Knob "pairs_grid" > 0 caps both grid dimensions of the data kernel as it does for correct_kernel
+ * (tests); like every knob it does not change results.
+ * When to prefer ecamd_rs_decode_multi: DESIGN.md "Decode from device masks", INTEGRATION.md. */
+int ecamd_rs_decode_masks(int k, int m, const uint32_t *d_lost, int rebuild_parity, void *base,
+                          int64_t stripe_stride, int64_t frag_stride, int64_t blocksize, int nstripes,
+                          uint32_t *d_result /* may be NULL */, uint32_t *d_counts /* 3 words, may be NULL */,
+                          void *stream);
+/* Launches of decode_masks_kernel (the data kernel) enqueued by this process: one per call with a
+ * non-empty batch. */
+long long ecamd_decode_masks_launches(void);
+
 /* ---- flat_xor_hd on strided batches: the reference's xor_code_encode,
  * xor_hd_decode (decode_parity as its argument) and xor_reconstruct_one
  * (src/builtin/xor_codes/xor_code.c:180-314, xor_hd_code.c:574-662) replayed exactly per erasure
@@ -567,6 +612,17 @@ int ecamd_frame_reconstruct(int backend, int k, int m, int hd, int checksum, con
 int ecamd_frame_verify(int nfrag, int64_t blocksize, int legacy, const void *d_frags,
                        int64_t stripe_stride, int64_t frag_stride, int nstripes, uint32_t *d_status,
                        uint32_t *d_crc, void *stream);
+/* The glue from the audit to ecamd_rs_decode_masks: d_masks[s] (nstripes uint32, device memory) gets
+ * bit f when d_frag_status[s*nfrag + f] & bits is non-zero; d_frag_status has the layout
+ * ecamd_frame_verify writes, nfrag <= 32.  One small kernel, asynchronous on `stream`.  With it
+ *   ecamd_frame_verify -> ecamd_frame_status_masks(bits = 1 << 4) -> ecamd_rs_decode_masks(base = d_frags + 80)
+ * heals payload damage of framed stripes on one stream with one wait at the end: the header still
+ * holds the original payload's CRC32, so the rebuilt payload matches it again.  Fragments with a bad
+ * HEADER (bits 0-3) are not covered: the decode rebuilds payloads only and no header is restamped, so
+ * do not pass those bits unless the headers are rewritten by other means (ecamd_frame_reconstruct).
+ * ECAMD_EINVAL (nothing written) for null arrays, nfrag < 1 or > 32, nstripes < 0. */
+int ecamd_frame_status_masks(int nfrag, const uint32_t *d_frag_status, uint32_t bits, int nstripes,
+                             uint32_t *d_masks, void *stream);
 /* zlib crc32(0, buf, len) (legacy = 0) or liberasurecode_crc32_alt(0, buf, len) (legacy = 1) of
  * every buffer d_base + s*stripe_stride + f*frag_stride, f < nfrag: d_crc[s*nfrag + f]. */
 int ecamd_crc32(int legacy, const void *d_base, int64_t stripe_stride, int64_t frag_stride,

@@ -182,6 +182,10 @@ def dev():
         _proto(d, "ecamd_xor_check_fused_launches", C.c_longlong, [])
         _proto(d, "ecamd_xor_locate_fused_launches", C.c_longlong, [])
         _proto(d, "ecamd_locate_prebuild", C.c_int, [C.c_int, C.c_int, VP, C.c_char_p, C.c_char_p])
+        _proto(d, "ecamd_rs_decode_masks", C.c_int,
+               [C.c_int, C.c_int, VP, C.c_int, VP, C.c_int64, C.c_int64, C.c_int64, C.c_int, VP, VP, VP])
+        _proto(d, "ecamd_decode_masks_launches", C.c_longlong, [])
+        _proto(d, "ecamd_frame_status_masks", C.c_int, [C.c_int, VP, C.c_uint32, C.c_int, VP, VP])
         _proto(d, "ecamd_percall_reset", None, [])
         _proto(d, "ecamd_percall_status", C.c_int, [])
         _proto(d, "ecamd_fault_inject", C.c_int, [C.c_char_p, C.c_int])

@@ -62,10 +62,13 @@ int side_join(int dev, void* stream);
 // the same stream, whose partials use slot 0).
 // Slot 4: the small-launch fused CRC's counter and partials (ecamd_map_apply_strided_crc).  A slot is
 // zeroed when it is (re)allocated.  Slot 5: the fragments the checks and locates of ecamd_check.hip
-// compute to compare the stored ones against (generic stage; at most kCheckScratchBytes).
-constexpr int kStreamScratchSlots = 6;
+// compute to compare the stored ones against (generic stage; at most kCheckScratchBytes).  Slot 6: the
+// per-stripe records of ecamd_rs_decode_masks (ecamd_decode_masks.hip; 560 bytes per stripe of the
+// largest batch seen).
+constexpr int kStreamScratchSlots = 7;
 constexpr int kSmallCrcScratchSlot = 4;
 constexpr int kCheckScratchSlot = 5;
+constexpr int kMasksPlanScratchSlot = 6;
 constexpr size_t kCheckScratchBytes = size_t(64) << 20;
 int stream_scratch(int dev, void* stream, int slot, size_t words, uint32_t** out);
 // A framed call in progress on (dev, stream): its context is not released until the call has

@@ -334,6 +334,43 @@ def xor_correct(k, m, hd, lay: Layout, stream=None, missing=()):
         _s(stream)), lay, stream, "xor_correct", False)
 
 
+def rs_decode_masks(k, m, lost_masks, lay: Layout, rebuild_parity=True, stream=None):
+    """ecamd_rs_decode_masks: rebuild in place the fragments each stripe lost, lost_masks[s] the mask of
+    stripe s (bit f: fragment f is lost).  The masks are uploaded to device memory, where the call reads
+    them; there is no host wait inside the call.  Returns (result, counts) after this function's own
+    synchronise: result[s] = fragments rebuilt, 0 for an empty mask, 0x80000000 | popcount for a mask that
+    cannot be recovered (that stripe is not written); counts = (left alone, rebuilt, unrecoverable).
+    blocksize must be even, m <= 8."""
+    n = max(lay.nstripes, 1)
+    masks = np.ascontiguousarray(np.asarray(lost_masks, dtype=np.uint32).reshape(-1))
+    if masks.size != lay.nstripes:
+        raise ValueError("one mask per stripe: %d masks, %d stripes" % (masks.size, lay.nstripes))
+    buf = DeviceBuffer(8 * n + 16)
+    try:
+        check(dev().ecamd_memset(buf.ptr, 0, 8 * n + 16), "memset")
+        if lay.nstripes:
+            buf.upload(masks)
+        check(dev().ecamd_rs_decode_masks(k, m, buf.ptr, int(rebuild_parity), lay.buf.ptr, lay.stripe_stride,
+                                          lay.frag_stride, lay.blocksize, lay.nstripes, buf.ptr + 4 * n,
+                                          buf.ptr + 8 * n, _s(stream)), "rs_decode_masks")
+        if stream is not None:
+            stream.synchronize()
+        else:
+            check(dev().ecamd_synchronize(), "synchronize")
+        words = buf.download(8 * n + 16).view(np.uint32)
+        return words[n:n + lay.nstripes].copy(), tuple(int(c) for c in words[2 * n:2 * n + 3])
+    finally:
+        buf.free()
+
+
+def frame_status_masks(nfrag, d_frag_status, bits, nstripes, d_masks, stream=None):
+    """ecamd_frame_status_masks: d_masks[s] (device address) gets bit f when word s*nfrag + f of
+    d_frag_status (device address, as ecamd_frame_verify writes it) has any of `bits`.  Asynchronous on
+    `stream`: the masks are meant for ecamd_rs_decode_masks on the same stream."""
+    check(dev().ecamd_frame_status_masks(nfrag, d_frag_status, bits, nstripes, d_masks, _s(stream)),
+          "frame_status_masks")
+
+
 def xor_scrub(k, m, hd, lay: Layout, stream=None):
     """ecamd_xor_scrub on full flat_xor_hd stripes: locate, then repair in place every stripe with
     exactly one suspect.  Returns (status, suspects, (n_clean, n_repaired, n_unlocated)) as rs_scrub;
