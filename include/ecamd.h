@@ -529,6 +529,9 @@ int ecamd_xor_reconstruct(int k, int m, int hd, const int *missing, int dest, vo
 int ecamd_xor_decode_multi(int k, int m, int hd, const int *missing, int missing_stride,
                            int decode_parity, void *base, int64_t stripe_stride, int64_t frag_stride,
                            int64_t blocksize, int nstripes, void *stream);
+/* Launches of xor_stream_kernel enqueued by this process, with or without the copy-through (tests pin
+ * which kernel ran: passes of at most "small_chunks" chunks take xor_small_kernel and do not count). */
+long long ecamd_xor_stream_launches(void);
 
 /* ---- synchronous host-buffer execution (used by the per-call drop-in ABIs) ----
  * Pooled pinned staging + two streams, chunked so host copies overlap PCIe and the kernel.

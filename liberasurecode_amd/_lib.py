@@ -181,6 +181,7 @@ def dev():
         _proto(d, "ecamd_locate_fused_launches", C.c_longlong, [])
         _proto(d, "ecamd_xor_check_fused_launches", C.c_longlong, [])
         _proto(d, "ecamd_xor_locate_fused_launches", C.c_longlong, [])
+        _proto(d, "ecamd_xor_stream_launches", C.c_longlong, [])
         _proto(d, "ecamd_locate_prebuild", C.c_int, [C.c_int, C.c_int, VP, C.c_char_p, C.c_char_p])
         _proto(d, "ecamd_rs_decode_masks", C.c_int,
                [C.c_int, C.c_int, VP, C.c_int, VP, C.c_int64, C.c_int64, C.c_int64, C.c_int, VP, VP, VP])

@@ -1367,6 +1367,7 @@ int launch_gf16(const ecamd_map* map, ApplyArgs base_args, const int64_t* in_off
 }
 
 constexpr int64_t kXorNarrowMin = 256 << 10;  // fragment bytes from which flat XOR takes 1 KiB tiles
+std::atomic<long long> g_xor_stream_launches{0};  // xor_stream_kernel launches enqueued by this process
 
 // copy_off (framed flat-XOR encode): input j is also stored at base_args.copy_base + s*copy_stride +
 // copy_off[j] by the first row group's launches -- whole stream-kernel tiles only: ECAMD_EINVAL, with
@@ -1470,6 +1471,7 @@ int launch_xor(const uint32_t* masks, int R, int K, ApplyArgs base_args, const i
                         default: hipLaunchKernelGGL((xor_stream_kernel<8, false>), grid, block, lds, st, c); break;
                         }
                     }
+                    g_xor_stream_launches.fetch_add(1, std::memory_order_relaxed);
                     HIP_TRY(hipGetLastError());
                     return 0;
                 });
@@ -3556,5 +3558,6 @@ int ecamd_bitslice_timeline(void* buf, unsigned records)
 // what launch_bitslice counted for ecamd_check.hip
 long long ecamd_check_fused_launches(void) { return g_check_fused.load(std::memory_order_relaxed); }
 long long ecamd_locate_fused_launches(void) { return g_locate_fused.load(std::memory_order_relaxed); }
+long long ecamd_xor_stream_launches(void) { return g_xor_stream_launches.load(std::memory_order_relaxed); }
 
 }  // extern "C"
