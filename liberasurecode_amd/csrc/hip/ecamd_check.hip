@@ -27,7 +27,10 @@
 // Correct stage (ecamd_rs_correct, ecamd_xor_correct): after the locate or the pair stage,
 // correct_kernel reads the three words of each stripe and XORs the error values of a located fragment
 // or pair into the stored words -- on the same stream, with no host wait (DESIGN.md "Correct on the
-// device").
+// device").  The device tables of the pair and correct stages are laid out and built here, beside the
+// kernels that read them (PairsTable / check_map_pairs, CorrectTable / check_map_correct /
+// xor_correct_table); the cached check map of ecamd_rs.hip only owns the memory of its two (OnceTable).
+// stripe_grid, the grid of the stripe-by-stripe kernels, is shared with ecamd_decode_masks.hip.
 //
 // Flat XOR with fragments missing (ecamd_xor_check_degraded, ecamd_xor_locate_degraded,
 // ecamd_xor_correct_degraded): the rows of ecamd_xor_check_plan_degraded through the same stages -- the
@@ -54,13 +57,6 @@
 using namespace ecamd;
 
 namespace {
-
-#define HIP_TRY(expr)                                                                      \
-    do {                                                                                   \
-        hipError_t e_ = (expr);                                                            \
-        if (e_ != hipSuccess)                                                              \
-            return dev_fail(ECAMD_EHIP, "%s: %s", #expr, hipGetErrorString(e_));           \
-    } while (0)
 
 struct CheckCmpArgs {
     const uint8_t* base;  // stored: row r of stripe s at base + s*stripe_stride + off[r]
@@ -215,8 +211,21 @@ __global__ void __launch_bounds__(256) locate_finalize_kernel(const uint32_t* st
 // ---- rs_vand, two bad fragments: locate_pairs_kernel (ecamd_rs_locate_pairs) -------------------
 // Runs after a locate, on its results: a stripe that is dirty and has no suspect is read again, the
 // K inputs and the R checked fragments directly (no scratch), 4 bytes -- two words -- per lane at a
-// time.  The participants are the K inputs, then the R checked rows; the table (PairsTable,
-// ecamd_internal.hpp) holds what tests one of them and what tests a pair.
+// time.  The participants are the K inputs, then the R checked rows; the table (PairsTable) holds what
+// tests one of them and what tests a pair.
+//
+// The pair plan of a cached check map (rs_locate_pairs_plan, host/gf16.hpp) as the device table
+// locate_pairs_kernel reads (built by check_map_pairs below).  Entries of 2 + R words: [0] fragment a |
+// fragment b << 8 | pivot row p << 16 | pivot row q << 24, [1] the rows a single participant must leave
+// non-zero -- exactly those --, [2 + r] L[r][0] | L[r][1] << 16.  First the K + R single participants (b
+// and q 0xff; L[r][0] = column[r] / column[p], p its first non-zero row), then the pairs that can be
+// tested (dependent ones left out).  `exact`: any four columns of [A | I] are independent, so the pair is
+// unique; dev is null when it is not, or when R < 4 (the call then leaves d_pairs zero).  At most 18 KiB.
+struct PairsTable {
+    const uint32_t* dev = nullptr;
+    int singles = 0, pairs = 0, stride = 0;
+    bool exact = false;
+};
 constexpr int kPairsMaxRows = 31;  // K + R <= 32; R >= 4 leaves K <= 28
 struct PairsArgs {
     const uint8_t* base;  // participant c of stripe s at base + s*stripe_stride + off[c]
@@ -361,11 +370,19 @@ __global__ void __launch_bounds__(256) pairs_finalize_kernel(uint32_t* pairs, in
 
 std::atomic<long long> g_pairs_launches{0};
 
+// PairsArgs / CorrectArgs cmask of the R x K matrix A: [r*16 + b] the inputs j whose A[r][j] has bit b.
+void fill_cmask(const std::vector<int>& A, int K, int R, uint32_t* cmask)
+{
+    for (int r = 0; r < R; r++)
+        for (int j = 0; j < K; j++)
+            for (int b = 0; b < 16; b++)
+                if ((A[static_cast<size_t>(r) * K + j] >> b) & 1) cmask[r * 16 + b] |= 1u << j;
+}
+
 // The pair stage of one call, after locate_finalize_kernel on the same stream, which has set d_pairs
-// to 0: with R >= 4 and a table, locate_pairs_kernel and its finalize.  The grid: a chunk per 16 passes
-// of 256 units, at most 64, by as many stripe slots as keep it within 4096 workgroups -- on a clean
-// batch the launch costs what its empty workgroups cost (11 us for 16384 of them, traced); knob
-// pairs_grid > 0 caps both dimensions.
+// to 0: with R >= 4 and a table, locate_pairs_kernel and its finalize.  The grid (stripe_grid): a chunk
+// per 16 passes of 256 units -- on a clean batch the launch costs what its empty workgroups cost (11 us
+// for 16384 of them, traced).
 int locate_pairs(const std::vector<int>& A, int K, int R, const PairsTable& t, const uint8_t* base, int64_t stripe_stride,
                  const int64_t* in_off, const int64_t* chk_off, int64_t blocksize, int nstripes, const uint32_t* d_status,
                  const uint32_t* d_suspects, uint32_t* d_pairs, hipStream_t st)
@@ -381,23 +398,15 @@ int locate_pairs(const std::vector<int>& A, int K, int R, const PairsTable& t, c
     a.len = blocksize;
     for (int j = 0; j < K; j++) a.off[j] = in_off[j];
     for (int r = 0; r < R; r++) a.off[K + r] = chk_off[r];
-    for (int r = 0; r < R; r++)
-        for (int j = 0; j < K; j++)
-            for (int b = 0; b < 16; b++)
-                if ((A[static_cast<size_t>(r) * K + j] >> b) & 1) a.cmask[r * 16 + b] |= 1u << j;
+    fill_cmask(A, K, R, a.cmask);
     a.nstripes = nstripes;
     a.K = K;
     a.R = R;
     a.singles = t.singles;
     a.npairs = t.pairs;
     a.stride = t.stride;
-    const int64_t units = (blocksize + 3) >> 2;
-    int chunks = static_cast<int>(std::clamp<int64_t>((units + 4095) / 4096, 1, 64)), slots = std::min(nstripes, 4096 / chunks);
-    const int cap = g_tune.pairs_grid;
-    if (cap > 0) {
-        chunks = std::min(chunks, cap);
-        slots = std::min(slots, cap);
-    }
+    int chunks = 0, slots = 0;
+    stripe_grid((blocksize + 3) >> 2, nstripes, chunks, slots);
     const dim3 grid(static_cast<unsigned>(chunks), static_cast<unsigned>(slots)), block(256);
     const size_t lds = (static_cast<size_t>(R) * 256 + 1) * sizeof(uint32_t);
     switch ((K + 3) / 4) {  // K <= 28
@@ -423,8 +432,18 @@ int locate_pairs(const std::vector<int>& A, int K, int R, const PairsTable& t, c
 // e_c = scale[c] * S_pivot[c] in every word, and a located pair {a, b} with pivot rows (p, q) has
 // (e_a, e_b) = inv(M) (S_p, S_q), M the 2 x 2 minor the pair plan picked.  XORing the error value into
 // the stored word gives the codeword that agrees with every other participant -- the fragment a
-// decode would write, byte for byte -- so only the words that are wrong are written.  The table
-// (CorrectTable, ecamd_internal.hpp) is device memory kept with the cached check map.
+// decode would write, byte for byte -- so only the words that are wrong are written.
+//
+// The correction plan (rs_correct_plan, host/gf16.hpp) as the device table correct_kernel reads.  Words
+// [0, 32): for fragment f, participant c | pivot row << 8 | scale << 16, all ones for a fragment that
+// takes no part.  With `pairs` (R >= 2), from word 32 three words per pair of participants a < b in the
+// pair plan's order: pivot row p | pivot row q << 8 (0xff each for dependent columns), minv[0] | minv[1]
+// << 16, minv[2] | minv[3] << 16.  At most 32 + 3 * 496 words.  rs_vand: check_map_correct below, kept
+// with the cached check map; flat XOR: the 32 words alone (xor_correct_table).
+struct CorrectTable {
+    const uint32_t* dev = nullptr;
+    bool pairs = false;
+};
 struct CorrectArgs {
     uint8_t* base;  // participant c of stripe s at base + s*stripe_stride + off[c]
     const uint32_t* status;
@@ -566,8 +585,7 @@ std::atomic<long long> g_correct_launches{0};
 
 // The correction of one call, after the locate's (or the pair stage's) last kernel on the same
 // stream: correct_kernel and, with d_counts, the counts.  Nothing here waits for the stream or copies
-// to the host -- the case of every stripe is decided on the device.  The grid as locate_pairs, knob
-// pairs_grid included: > 0 caps both dimensions.
+// to the host -- the case of every stripe is decided on the device.  The grid as locate_pairs.
 int correct_located(const std::vector<int>& A, int K, int R, const CorrectTable& t, uint8_t* base, int64_t stripe_stride,
                     const int64_t* in_off, const int64_t* chk_off, int64_t blocksize, int nstripes, const uint32_t* d_status,
                     const uint32_t* d_suspects, const uint32_t* d_pairs, uint32_t* d_counts, hipStream_t st)
@@ -583,20 +601,12 @@ int correct_located(const std::vector<int>& A, int K, int R, const CorrectTable&
         a.len = blocksize;
         for (int j = 0; j < K; j++) a.off[j] = in_off[j];
         for (int r = 0; r < R; r++) a.off[K + r] = chk_off[r];
-        for (int r = 0; r < R; r++)
-            for (int j = 0; j < K; j++)
-                for (int b = 0; b < 16; b++)
-                    if ((A[static_cast<size_t>(r) * K + j] >> b) & 1) a.cmask[r * 16 + b] |= 1u << j;
+        fill_cmask(A, K, R, a.cmask);
         a.nstripes = nstripes;
         a.K = K;
         a.P = K + R;
-        const int64_t units = (blocksize + 3) >> 2;
-        int chunks = static_cast<int>(std::clamp<int64_t>((units + 4095) / 4096, 1, 64)), slots = std::min(nstripes, 4096 / chunks);
-        const int cap = g_tune.pairs_grid;
-        if (cap > 0) {
-            chunks = std::min(chunks, cap);
-            slots = std::min(slots, cap);
-        }
+        int chunks = 0, slots = 0;
+        stripe_grid((blocksize + 3) >> 2, nstripes, chunks, slots);
         const dim3 grid(static_cast<unsigned>(chunks), static_cast<unsigned>(slots)), block(256);
         switch ((K + 3) / 4) {  // K <= 31
         case 1: hipLaunchKernelGGL(correct_kernel<1>, grid, block, 0, st, a); break;
@@ -1072,6 +1082,103 @@ int run_check(int dev, const CheckPlan& p, const void* base, int64_t stripe_stri
                            blocksize, nstripes, d_status, d_suspects, d_pairs, d_counts, st);
 }
 
+// The pair table of a cached check map (PairsTable above), made at the first call that asks for it and
+// kept with the map (cm.pairs: freed with the entry, not counted against the map cache's byte limit).
+int check_map_pairs(const CheckMap& cm, PairsTable& out)
+{
+    out = PairsTable();
+    OnceTable* t = cm.pairs;
+    if (!t || !cm.coeff) return 0;
+    const std::vector<int>&inputs = *cm.inputs, &outputs = *cm.checked;
+    const int K = static_cast<int>(inputs.size()), R = static_cast<int>(outputs.size());
+    std::call_once(t->once, [&] {
+        const PairPlan plan = rs_locate_pairs_plan(*cm.coeff, R, K);
+        if (!plan.pairs || !plan.independent4) return;  // no table: d_pairs stays zero
+        const GF16& gf = GF16::get();
+        const int P = K + R;
+        auto frag = [&](int c) { return static_cast<uint32_t>(c < K ? inputs[c] : outputs[c - K]); };
+        std::vector<uint32_t> tab;
+        for (int c = 0; c < P; c++) {  // the single participants
+            std::vector<int> col(static_cast<size_t>(R));
+            int p = -1;
+            uint32_t rows = 0;
+            for (int r = 0; r < R; r++) {
+                col[r] = c < K ? (*cm.coeff)[static_cast<size_t>(r) * K + c] : (r == c - K);
+                if (col[r]) {
+                    if (p < 0) p = r;
+                    rows |= 1u << r;
+                }
+            }
+            // (an all-zero column cannot be independent of the others)
+            tab.push_back(frag(c) | 0xffu << 8 | static_cast<uint32_t>(std::max(p, 0)) << 16 | 0xffu << 24);
+            tab.push_back(rows);
+            for (int r = 0; r < R; r++) tab.push_back(p < 0 ? 0u : static_cast<uint32_t>(gf.mul(col[r], gf.inv(col[p]))));
+        }
+        int i = 0;
+        for (int a = 0; a < P; a++)
+            for (int b = a + 1; b < P; b++, i++) {
+                const int p = plan.pivot[static_cast<size_t>(i) * 2], q = plan.pivot[static_cast<size_t>(i) * 2 + 1];
+                if (p < 0) continue;
+                tab.push_back(frag(a) | frag(b) << 8 | static_cast<uint32_t>(p) << 16 | static_cast<uint32_t>(q) << 24);
+                tab.push_back(0u);
+                for (int r = 0; r < R; r++) {
+                    const int* l = &plan.L[(static_cast<size_t>(i) * R + r) * 2];
+                    tab.push_back(static_cast<uint32_t>(l[0]) | static_cast<uint32_t>(l[1]) << 16);
+                }
+            }
+        const void* d = nullptr;
+        if ((t->rc = upload_table("pair table", tab.data(), tab.size() * sizeof(uint32_t), &d))) return;
+        t->dev = static_cast<const uint32_t*>(d);
+        t->words = tab.size();
+    });
+    if (t->rc) return dev_fail(ECAMD_EHIP, "pair table upload failed");
+    if (!t->dev) return 0;
+    out.dev = t->dev;
+    out.singles = K + R;
+    out.stride = 2 + R;
+    out.pairs = static_cast<int>(t->words) / out.stride - out.singles;  // the entries after the singles
+    out.exact = true;
+    return 0;
+}
+
+// The correction table of a cached check map (CorrectTable above), the same way (cm.correct).
+int check_map_correct(const CheckMap& cm, CorrectTable& out)
+{
+    out = CorrectTable();
+    OnceTable* t = cm.correct;
+    if (!t || !cm.coeff) return 0;  // nothing checked: nothing to correct
+    std::call_once(t->once, [&] {
+        const std::vector<int>&inputs = *cm.inputs, &outputs = *cm.checked;
+        const int K = static_cast<int>(inputs.size()), R = static_cast<int>(outputs.size());
+        const CorrectPlan plan = rs_correct_plan(*cm.coeff, R, K);
+        const int P = K + R;
+        if (P > 32 || static_cast<int>(plan.pivot.size()) != P) return;
+        std::vector<uint32_t> tab(32, 0xffffffffu);
+        for (int c = 0; c < P; c++) {
+            const int f = c < K ? inputs[c] : outputs[c - K];
+            if (f < 0 || f >= 32 || plan.pivot[c] < 0) continue;
+            tab[static_cast<size_t>(f)] = static_cast<uint32_t>(c) | static_cast<uint32_t>(plan.pivot[c]) << 8 |
+                                          static_cast<uint32_t>(plan.scale[c]) << 16;
+        }
+        for (int i = 0; i < plan.pairs; i++) {
+            const int p = plan.pair_pivot[static_cast<size_t>(i) * 2], q = plan.pair_pivot[static_cast<size_t>(i) * 2 + 1];
+            const int* w = &plan.minv[static_cast<size_t>(i) * 4];
+            tab.push_back(p < 0 ? 0xffffu : static_cast<uint32_t>(p) | static_cast<uint32_t>(q) << 8);
+            tab.push_back(static_cast<uint32_t>(w[0]) | static_cast<uint32_t>(w[1]) << 16);
+            tab.push_back(static_cast<uint32_t>(w[2]) | static_cast<uint32_t>(w[3]) << 16);
+        }
+        // once per cached map, before anything of the call is enqueued: a few KiB, as the pair table
+        const void* d = nullptr;
+        if ((t->rc = upload_table("correction table", tab.data(), tab.size() * sizeof(uint32_t), &d))) return;
+        t->dev = static_cast<const uint32_t*>(d);
+        t->words = tab.size();
+    });
+    if (t->rc) return dev_fail(ECAMD_EHIP, "correction table upload failed");
+    out.dev = t->dev;
+    out.pairs = t->words > 32;
+    return 0;
+}
+
 // ecamd_rs_check (locate false), ecamd_rs_locate and ecamd_rs_locate_pairs (pairs true): a bad layout
 // is reported before too many missing fragments, so it is checked before the plan is made.
 int rs_call(bool locate, int k, int m, const int* missing, const void* base, int64_t stripe_stride, int64_t frag_stride,
@@ -1100,7 +1207,7 @@ int rs_call(bool locate, int k, int m, const int* missing, const void* base, int
                      stream, pairs ? d_pairs : nullptr, fix_base, d_counts);
 }
 
-// The correction table of a flat XOR code (CorrectTable, ecamd_internal.hpp) from its check plan:
+// The correction table of a flat XOR code (CorrectTable above) from its check plan:
 // fragment f is participant f, its pivot the lowest row of sig[f], every scale 1.  Device memory made
 // at the first call that asks, per (device, k, m, hd, mask of lost fragments), and kept for the life of
 // the process (a few accepted codes and the loss patterns a caller meets, 128 bytes each).  With
@@ -1134,13 +1241,8 @@ int xor_correct_table(int dev, int k, int m, int hd, uint32_t lost, const std::v
                 tab[f] = part < 0 || row < 0 ? 0xffffffffu : static_cast<uint32_t>(part) | static_cast<uint32_t>(row) << 8 | 1u << 16;
             }
         }
-        void* d = nullptr;
-        HIP_TRY(hipMalloc(&d, sizeof(tab)));
-        const hipError_t err = hipMemcpy(d, tab, sizeof(tab), hipMemcpyHostToDevice);  // once per code, before anything is enqueued
-        if (err != hipSuccess) {
-            (void)hipFree(d);
-            return dev_fail(ECAMD_EHIP, "correction table: %s", hipGetErrorString(err));
-        }
+        const void* d = nullptr;  // once per code, before anything is enqueued
+        if (const int rc = upload_table("correction table", tab, sizeof(tab), &d)) return rc;
         slot = static_cast<const uint32_t*>(d);
     }
     out.dev = slot;
@@ -1287,16 +1389,25 @@ int prebuild_plan(const char* what, int k, int m, const int* missing, const char
 {
     if (!arch || !dir) return dev_fail(ECAMD_EINVAL, "null arch / dir");
     if (k <= 0 || m < 0 || k + m > 32) return dev_fail(ECAMD_EINVAL, "%s needs k + m <= 32 (k=%d m=%d)", what, k, m);
-    std::vector<int> miss;
-    if (missing)
-        for (int i = 0; missing[i] > -1; i++) miss.push_back(missing[i]);
-    const std::vector<int> G = rs_generator(k, m);
-    if (G.empty() || rs_check_map(G, k, m, miss, fm) != 0)
-        return dev_fail(ECAMD_EINVAL, "too many missing fragments (%zu > m=%d)", miss.size(), m);
-    return 0;
+    return rs_vand_plan(4, k, m, missing, -1, 0, fm);
 }
 
 }  // namespace
+
+namespace ecamd {
+
+void stripe_grid(int64_t units, int nstripes, int& chunks, int& slots)
+{
+    chunks = static_cast<int>(std::clamp<int64_t>((units + 4095) / 4096, 1, 64));
+    slots = std::min(nstripes, 4096 / chunks);
+    const int cap = g_tune.pairs_grid;
+    if (cap > 0) {
+        chunks = std::min(chunks, cap);
+        slots = std::min(slots, cap);
+    }
+}
+
+}  // namespace ecamd
 
 extern "C" {
 

@@ -21,7 +21,6 @@
 #include <vector>
 
 #include "../host/gf16.hpp"
-#include "../host/tune.hpp"
 #include "ecamd.h"
 #include "ecamd_internal.hpp"
 #include "ecamd_masks_plan.hpp"
@@ -30,13 +29,6 @@
 using namespace ecamd;
 
 namespace {
-
-#define HIP_TRY(expr)                                                                      \
-    do {                                                                                   \
-        hipError_t e_ = (expr);                                                            \
-        if (e_ != hipSuccess)                                                              \
-            return dev_fail(ECAMD_EHIP, "%s: %s", #expr, hipGetErrorString(e_));           \
-    } while (0)
 
 constexpr int kPlanLanes = 64;
 
@@ -222,13 +214,8 @@ int masks_generator(int dev, int k, int m, const uint16_t** out)
         const std::vector<int> G = rs_generator(k, m);
         if (G.empty()) return dev_fail(ECAMD_EINVAL, "no generator for k=%d m=%d", k, m);
         const std::vector<uint16_t> g16(G.begin(), G.end());
-        void* d = nullptr;
-        HIP_TRY(hipMalloc(&d, g16.size() * sizeof(uint16_t)));
-        const hipError_t err = hipMemcpy(d, g16.data(), g16.size() * sizeof(uint16_t), hipMemcpyHostToDevice);  // once per code
-        if (err != hipSuccess) {
-            (void)hipFree(d);
-            return dev_fail(ECAMD_EHIP, "generator upload: %s", hipGetErrorString(err));
-        }
+        const void* d = nullptr;  // once per code
+        if (const int rc = upload_table("generator upload", g16.data(), g16.size() * sizeof(uint16_t), &d)) return rc;
         slot = static_cast<const uint16_t*>(d);
     }
     *out = slot;
@@ -290,15 +277,8 @@ int ecamd_rs_decode_masks(int k, int m, const uint32_t* d_lost, int rebuild_pari
     a.len = blocksize;
     a.nstripes = nstripes;
     a.k = k;
-    // the grid of correct_located: a tile column per 16 tiles, at most 64, by as many stripe slots as keep
-    // it within 4096 workgroups; knob pairs_grid > 0 caps both dimensions
-    const int64_t chunks = (blocksize + 15) >> 4;
-    int cols = static_cast<int>(std::clamp<int64_t>((chunks + 4095) / 4096, 1, 64)), slots = std::min(nstripes, 4096 / cols);
-    const int cap = g_tune.pairs_grid;
-    if (cap > 0) {
-        cols = std::min(cols, cap);
-        slots = std::min(slots, cap);
-    }
+    int cols = 0, slots = 0;  // a tile column per 16 tiles of 4096 bytes (stripe_grid's units: 16-byte chunks)
+    stripe_grid((blocksize + 15) >> 4, nstripes, cols, slots);
     const dim3 grid(static_cast<unsigned>(cols), static_cast<unsigned>(slots));
     const int groups = (k + 3) / 4, W = m <= 2 ? 2 : m <= 4 ? 4 : 8;
     const size_t lds = static_cast<size_t>(k) * 64 * 2 * W;

@@ -23,13 +23,6 @@ using namespace ecamd;
 
 namespace {
 
-#define HIP_TRY(expr)                                                                      \
-    do {                                                                                   \
-        hipError_t e_ = (expr);                                                            \
-        if (e_ != hipSuccess)                                                              \
-            return dev_fail(ECAMD_EHIP, "%s: %s", #expr, hipGetErrorString(e_));           \
-    } while (0)
-
 constexpr int kBackendXor = 3;   // EC_BACKEND_FLAT_XOR_HD
 constexpr int kBackendRs = 6;    // EC_BACKEND_LIBERASURECODE_RS_VAND
 constexpr uint32_t kLibecVersion = (1u << 16) | (8u << 8);  // LIBERASURECODE_VERSION 1.8.0
@@ -44,7 +37,7 @@ bool legacy_crc()
 }
 
 struct DevImage {
-    uint32_t* d = nullptr;
+    const uint32_t* d = nullptr;
     CrcImage img;
 };
 
@@ -60,8 +53,9 @@ int image(int dev, bool legacy, int B, int J, int G, bool pos, const DevImage** 
         auto di = std::make_unique<DevImage>();
         di->img = build_crc_image(CrcMachine(legacy), B, J, G, pos);
         const size_t bytes = di->img.words.size() * sizeof(uint32_t);
-        HIP_TRY(hipMalloc(&di->d, bytes));
-        HIP_TRY(hipMemcpy(di->d, di->img.words.data(), bytes, hipMemcpyHostToDevice));
+        const void* d = nullptr;
+        if (const int rc = upload_table("CRC image", di->img.words.data(), bytes, &d)) return rc;
+        di->d = static_cast<const uint32_t*>(d);
         it = g_images.emplace(key, std::move(di)).first;
     }
     *out = it->second.get();
@@ -129,13 +123,12 @@ int64_t blocksize_of(const Code& c, uint64_t size)
     return aligned / c.k;
 }
 
-bool a16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 int check_frames(const void* frags, int64_t stripe_stride, int64_t frag_stride, int64_t bs,
                  int nfrag, int nstripes)
 {
     if (!frags || nstripes < 0) return dev_fail(ECAMD_EINVAL, "null fragments or nstripes < 0");
-    if (!a16(frags) || stripe_stride % 16 || frag_stride % 16)
+    if (!aligned16(frags) || stripe_stride % 16 || frag_stride % 16)
         return dev_fail(ECAMD_EINVAL, "fragment base and strides must be 16-byte aligned");
     if (frag_stride < kHeaderBytes + ((bs + 15) & ~int64_t(15)))
         return dev_fail(ECAMD_EINVAL, "frag_stride %lld < 80 + blocksize rounded to 16 (%lld)",
@@ -342,14 +335,14 @@ int xor_batch_check(const Code& c, const void* base, int64_t ss, int64_t fs, int
     int rc = check_code(c);
     if (rc) return rc;
     if (!base || nstripes < 0 || bs < 0) return dev_fail(ECAMD_EINVAL, "null base or negative sizes");
-    if (!a16(base) || ss % 16 || fs % 16) return dev_fail(ECAMD_EINVAL, "fragment addresses must be 16-byte aligned");
+    if (!aligned16(base) || ss % 16 || fs % 16) return dev_fail(ECAMD_EINVAL, "fragment addresses must be 16-byte aligned");
     if (fs < bs) return dev_fail(ECAMD_EINVAL, "frag_stride < blocksize");
     return 0;
 }
 
 // ---- fused CHKSUM_CRC32 framed encode (hip/ecamd_frame_fused.hip) ----
 
-std::map<std::pair<int, int>, uint32_t*> g_fused_images;  // (dev, legacy + 2 * mb) -> device image
+std::map<std::pair<int, int>, const uint32_t*> g_fused_images;  // (dev, legacy + 2 * mb) -> device image
 
 int fused_image(int dev, bool legacy, int mb, const uint32_t** out, int tile = 8192, int npos = 0,
                 bool nib = false)
@@ -362,10 +355,9 @@ int fused_image(int dev, bool legacy, int mb, const uint32_t** out, int tile = 8
         const std::vector<uint32_t> w =
             npos ? build_fused_crc_image_pos(CrcMachine(legacy), static_cast<uint64_t>(tile), npos, nib, mb)
                  : build_fused_crc_image(CrcMachine(legacy), static_cast<uint64_t>(tile), mb);
-        uint32_t* d = nullptr;
-        HIP_TRY(hipMalloc(&d, w.size() * sizeof(uint32_t)));
-        HIP_TRY(hipMemcpy(d, w.data(), w.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-        it = g_fused_images.emplace(key, d).first;
+        const void* d = nullptr;
+        if (const int rc = upload_table("fused CRC image", w.data(), w.size() * sizeof(uint32_t), &d)) return rc;
+        it = g_fused_images.emplace(key, static_cast<const uint32_t*>(d)).first;
     }
     *out = it->second;
     return 0;
@@ -763,7 +755,7 @@ int ecamd_frame_encode(int backend, int k, int m, int hd, int checksum, const vo
     auto* frags = static_cast<uint8_t*>(d_frags);
     hipStream_t st = static_cast<hipStream_t>(stream);
     uint8_t* p0 = frags + kHeaderBytes;
-    const bool aligned = a16(d_obj) && obj_stride % 16 == 0 && bs % 16 == 0;
+    const bool aligned = aligned16(d_obj) && obj_stride % 16 == 0 && bs % 16 == 0;
     if (backend == kBackendRs && aligned && static_cast<int64_t>(obj_size) == k * bs &&
         g_tune.frame_unfused == 0) {
         // The object fills the k payloads exactly (no padding): one launch reads it, copies the
@@ -785,7 +777,7 @@ int ecamd_frame_encode(int backend, int k, int m, int hd, int checksum, const vo
                        frag_stride, kHeaderBytes, k + m, bs, nstripes, nullptr,
                        header_args(c, checksum, bs, obj_size, 0), stream);
     }
-    if (backend == kBackendRs && a16(d_obj) && obj_stride % 16 == 0 && g_tune.frame_unfused == 0 &&
+    if (backend == kBackendRs && aligned16(d_obj) && obj_stride % 16 == 0 && g_tune.frame_unfused == 0 &&
         g_tune.frame_copy_padded != 0) {
         // Objects that do not fill the payloads exactly (any size: Swift's 1 MiB segments give
         // bs = 104858): the same copy-through launch reads each chunk j*bs of the object with
@@ -835,7 +827,7 @@ int ecamd_frame_encode(int backend, int k, int m, int hd, int checksum, const vo
                        frag_stride, kHeaderBytes, k + m, bs, nstripes, nullptr,
                        header_args(c, checksum, bs, obj_size, 0), stream);
     }
-    if (backend == kBackendXor && a16(d_obj) && obj_stride % 16 == 0 && g_tune.frame_unfused == 0 &&
+    if (backend == kBackendXor && aligned16(d_obj) && obj_stride % 16 == 0 && g_tune.frame_unfused == 0 &&
         g_tune.frame_xor_copy != 0 && g_tune.frame_copy_stream != 0 &&
         copy_fits32(k, frag_stride, bs, static_cast<int64_t>(obj_size))) {
         // flat XOR, copy-through (round 4): the whole 4 KiB tiles every object chunk holds in one
@@ -950,7 +942,7 @@ int ecamd_frame_decode(int backend, int k, int m, int hd, const int* missing, vo
     if (nmiss > m) return dev_fail(ECAMD_EINVAL, "%d fragments missing, at most m = %d", nmiss, m);
     auto* frags = static_cast<uint8_t*>(d_frags);
     uint8_t* p0 = frags + kHeaderBytes;
-    if (data_missing && backend == kBackendRs && d_obj && a16(d_obj) && obj_stride % 16 == 0 &&
+    if (data_missing && backend == kBackendRs && d_obj && aligned16(d_obj) && obj_stride % 16 == 0 &&
         g_tune.frame_unfused == 0 &&
         (static_cast<int64_t>(obj_size) == k * bs || g_tune.frame_copy_padded != 0)) {
         // One launch: the lost data are computed straight into the objects and the surviving data
@@ -959,7 +951,7 @@ int ecamd_frame_decode(int backend, int k, int m, int hd, const int* missing, vo
         return rs_decode_join(k, m, missing, p0, stripe_stride, frag_stride, d_obj, obj_stride, bs,
                               nstripes, stream, static_cast<int64_t>(obj_size));
     }
-    if (data_missing && backend == kBackendXor && d_obj && a16(d_obj) && obj_stride % 16 == 0 &&
+    if (data_missing && backend == kBackendXor && d_obj && aligned16(d_obj) && obj_stride % 16 == 0 &&
         g_tune.frame_unfused == 0 && g_tune.frame_xor_copy != 0 &&
         (static_cast<int64_t>(obj_size) == k * bs || g_tune.frame_copy_padded != 0)) {
         // flat XOR, as the RS decode-join: the plan is one 0 / 1 matrix over the surviving fragments
@@ -1004,12 +996,12 @@ int ecamd_frame_decode(int backend, int k, int m, int hd, const int* missing, vo
     if (!d_obj) return dev_fail(ECAMD_EINVAL, "null object buffer");
     JoinArgs ja{frags, stripe_stride, frag_stride, bs, static_cast<uint8_t*>(d_obj), obj_stride,
                 static_cast<int64_t>(obj_size), nstripes,
-                (a16(d_obj) && obj_stride % 16 == 0 && bs % 16 == 0) ? 1 : 0};
+                (aligned16(d_obj) && obj_stride % 16 == 0 && bs % 16 == 0) ? 1 : 0};
     if (copy_fits32(k, frag_stride, bs, static_cast<int64_t>(obj_size)) && bs >= 32 &&
         g_tune.frame_copy_stream != 0) {
         const CopyShape cs = copy_shape(bs);
         const int ja_knob = g_tune.frame_join_align;
-        const int align = (ja_knob == 1 || (ja_knob == 2 && bs % 16)) && a16(d_obj) && obj_stride % 16 == 0 ? 1 : 0;
+        const int align = (ja_knob == 1 || (ja_knob == 2 && bs % 16)) && aligned16(d_obj) && obj_stride % 16 == 0 ? 1 : 0;
         const int64_t span = static_cast<int64_t>(cs.threads) * cs.u;
         const dim3 grid(copy_grid(dev, bs / 16 + 2 + (align ? span - 1 : 0), k, nstripes, cs)), block(cs.threads);
         const bool dpp = g_tune.frame_copy_dpp != 0;
@@ -1110,7 +1102,7 @@ int ecamd_crc32(int legacy, const void* d_base, int64_t stripe_stride, int64_t f
     const StreamUse use(dev, stream);  // its stream context outlives this call
     if (!d_base || !d_crc || nfrag < 1 || len < 0 || nstripes < 0)
         return dev_fail(ECAMD_EINVAL, "bad crc32 arguments");
-    if (!a16(d_base) || stripe_stride % 16 || frag_stride % 16)
+    if (!aligned16(d_base) || stripe_stride % 16 || frag_stride % 16)
         return dev_fail(ECAMD_EINVAL, "crc32: base and strides must be 16-byte aligned");
     HeaderArgs none{};
     return run_crc(dev, legacy != 0, true, static_cast<const uint8_t*>(d_base), stripe_stride,

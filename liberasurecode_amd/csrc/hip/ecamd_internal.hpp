@@ -1,4 +1,5 @@
-// ecamd_internal.hpp -- helpers ecamd_device.hip shares with the other launch files.
+// ecamd_internal.hpp -- what the files of libecamd.so's device side take from each other, free of kernel
+// argument types (those: ecamd_launch.hpp).  Each section names the file that defines it.
 #pragma once
 #include <vector>
 #include <stddef.h>
@@ -9,11 +10,52 @@
 
 struct ecamd_map;
 
+// The HIP call failed: its text becomes the thread's error text and the caller returns ECAMD_EHIP
+// (needs <hip/hip_runtime.h> and ecamd.h where it is used).
+#define HIP_TRY(expr)                                                                      \
+    do {                                                                                   \
+        hipError_t e_ = (expr);                                                            \
+        if (e_ != hipSuccess)                                                              \
+            return ecamd::dev_fail(ECAMD_EHIP, "%s: %s", #expr, hipGetErrorString(e_));    \
+    } while (0)
+
 namespace ecamd {
+
+struct FragmentMap;
+
+// ---- ecamd_runtime.hip ----
+// The one writer of the thread's error text (ecamd_last_error): sets it and returns code.
+int dev_fail(int code, const char* fmt, ...);
+
+// "Upload a small table once and keep it": `bytes` of host words into device memory of their own, complete
+// on return; the buffer is freed again when the copy fails.  ECAMD_EHIP with the text "<what>: <HIP's>".
+// Where and for how long the pointer is cached is the caller's business.
+int upload_table(const char* what, const void* host, size_t bytes, const void** dev);
+// A device table made at most once and owned by whatever holds this (a cached map entry): made under
+// `once` with upload_table, `rc` its result, `words` its length in 32-bit words; freed with the owner.
+struct OnceTable {
+    std::once_flag once;
+    int rc = 0;
+    const uint32_t* dev = nullptr;
+    size_t words = 0;
+    ~OnceTable();
+};
+
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+// The apply entry points' rule: both bases, both stripe strides and every fragment offset are multiples
+// of 16 ("fragment addresses must be 16-byte aligned").
+inline bool frags_aligned16(const void* in_base, const void* out_base, int64_t in_stride, int64_t out_stride,
+                            const int64_t* in_off, int K, const int64_t* out_off, int R)
+{
+    bool ok = aligned16(in_base) && aligned16(out_base) && (in_stride % 16) == 0 && (out_stride % 16) == 0;
+    for (int j = 0; j < K; j++) ok = ok && (in_off[j] % 16) == 0;
+    for (int r = 0; r < R; r++) ok = ok && (out_off[r] % 16) == 0;
+    return ok;
+}
 
 // Asynchronous upload of a small host table (stripe list, pointer table) on `stream` through a
 // ring of pinned slots per (device, stream); call end() after enqueuing the launches that read
-// `dev` (ecamd_device.hip).
+// `dev`.
 struct StagedSlot;
 struct StagedRing;
 struct StagedUpload {
@@ -28,6 +70,7 @@ private:
     void* stream_ = nullptr;
 };
 
+// ---- ecamd_device.hip ----
 // Strided flat-XOR apply (ecamd_xor_apply_strided) over the stripes listed in the device array
 // d_list (logical stripe i is stripe d_list[i] of the layout); ECAMD_EINVAL when the stream
 // kernel cannot take the shape.
@@ -37,23 +80,16 @@ int xor_apply_list(const uint32_t* masks, int R, int K, void* base, int64_t stri
 
 int dev_ensure(int* dev_out);                       // 0, or ECAMD_ENODEV / ECAMD_EHIP
 int dev_cu_count(int dev);
-int dev_fail(int code, const char* fmt, ...);       // sets ecamd_last_error(), returns code
 // Stripes per launch of a strided pass split into launches of at most `limit` tiles per resident
 // workgroup (`slots` of them), as even as the stripes allow; limit 0: one launch (for_each_launch in
 // ecamd_device.hip, xor_check_fused in ecamd_check.hip).
 int launch_stripes(int nstripes, uint64_t tiles_per_stripe, uint64_t slots, uint64_t limit);
 
-// rs_vand encode whose k data inputs are read from objects (input j of stripe s at
-// obj + s*obj_stride + j*bs) and copied into payload j while the parity is computed
-// (payload f of stripe s at payload0 + s*stripe_stride + f*frag_stride).  Objects of obj_size
-// bytes (< 0: k*bs) are zero-padded past their end (prepare_fragments_for_encode).  16-byte aligned
-// object base / stride and payloads; bs even (the object side may be read unaligned).  from > 0 (a
-// multiple of 16): only bytes [from, bs) of every payload (the rest of a partly fused encode); to > 0:
-// only bytes [from, to).
+// ---- ecamd_runtime.hip: the per-(device, stream) contexts ----
 // Side stream of (dev, stream) for work beside the caller's launches (knob frame_tail_fork):
 // side_fork orders it after everything issued to `stream` so far, side_join orders `stream` after
 // everything issued to the side stream since.
-// The side stream and the scratch slots live in a per-(dev, stream) context (ecamd_device.hip),
+// The side stream and the scratch slots live in a per-(dev, stream) context (ecamd_runtime.hip),
 // bounded: ecamd_stream_destroy releases a stream's, and idle ones are released past a small cap.
 int side_fork(int dev, void* stream, void** side);
 int side_join(int dev, void* stream);
@@ -86,46 +122,35 @@ struct StreamUse {
 void stream_forget(void* stream);
 int stream_contexts();
 
-// What ecamd_check.hip (check, locate, scrub) takes from ecamd_device.hip.
+// ---- ecamd_rs.hip ----
+// The one rs_vand planner: the FragmentMap (host/gf16.hpp) of kind 0 encode, 1 decode (`rebuild`: parity
+// too), 2 reconstruct `dest`, 4 check (every surviving fragment beyond the first k) of the code (k, m)
+// with `missing` (-1 terminated, may be null) lost.  Host only, no device.  ECAMD_EINVAL with the texts
+// "bad k=.. m=..", "no generator for ..", "too many missing fragments (..)", "cannot reconstruct ..".
+int rs_vand_plan(int kind, int k, int m, const int* missing, int dest, int rebuild, FragmentMap& fm);
 // The cached check map of the rs_vand code (k, m) with `missing` (-1 terminated, may be null) lost:
 // the first k available fragments are the inputs, every other available one is checked.  `hold` keeps
 // the entry alive past its eviction from the map cache.  ECAMD_EINVAL for too many missing fragments.
+// `pairs`, `correct`: the entry's attachments for the device tables of the pair and correct stages, which
+// ecamd_check.hip makes on demand; they live and are freed with the entry (`hold`).
 struct CheckMap {
     const std::vector<int>* inputs = nullptr;   // fragment indices of the K inputs
     const std::vector<int>* checked = nullptr;  // fragment indices of the R checked fragments
     const std::vector<int>* coeff = nullptr;    // R x K, row-major (null when R == 0)
     const ecamd_map* map = nullptr;             // the same map for the apply calls (null when R == 0)
+    OnceTable* pairs = nullptr;
+    OnceTable* correct = nullptr;
     std::shared_ptr<const void> hold;
 };
 int check_map(int k, int m, const int* missing, CheckMap& out);
-// The pair plan of a cached check map (rs_locate_pairs_plan, host/gf16.hpp) as the device table
-// locate_pairs_kernel reads, made at the first call that asks for it and kept with the map.  Entries
-// of 2 + R words: [0] fragment a | fragment b << 8 | pivot row p << 16 | pivot row q << 24, [1] the
-// rows a single participant must leave non-zero -- exactly those --, [2 + r] L[r][0] | L[r][1] << 16.
-// First the K + R single participants (b and q 0xff; L[r][0] = column[r] / column[p], p its first
-// non-zero row), then the pairs that can be tested (dependent ones left out).  `exact`: any four
-// columns of [A | I] are independent, so the pair is unique; dev is null when it is not, or when
-// R < 4 (the call then leaves d_pairs zero).  The table is at most 18 KiB and is freed with its entry;
-// it is not counted against the map cache's byte limit.
-struct PairsTable {
-    const uint32_t* dev = nullptr;
-    int singles = 0, pairs = 0, stride = 0;
-    bool exact = false;
-};
-int check_map_pairs(const CheckMap& cm, PairsTable& out);
-// The correction plan of a cached check map (rs_correct_plan, host/gf16.hpp) as the device table
-// correct_kernel reads, made at the first call that asks for it and kept with the map, like the pair
-// table.  Words [0, 32): for fragment f, participant c | pivot row << 8 | scale << 16, all ones for a
-// fragment that takes no part.  With `pairs` (R >= 2), from word 32 three words per pair of participants
-// a < b in the pair plan's order: pivot row p | pivot row q << 8 (0xff each for dependent columns),
-// minv[0] | minv[1] << 16, minv[2] | minv[3] << 16.  At most 32 + 3 * 496 words; freed with its entry.
-// Flat XOR builds the 32 words alone (ecamd_check.hip): participant f, pivot the lowest bit of sig[f],
-// scale 1.
-struct CorrectTable {
-    const uint32_t* dev = nullptr;
-    bool pairs = false;
-};
-int check_map_correct(const CheckMap& cm, CorrectTable& out);
+
+// ---- ecamd_check.hip ----
+// The grid of the kernels that go stripe by stripe (locate_pairs_kernel, correct_kernel,
+// decode_masks_kernel): a chunk per 4096 units of a fragment, at most 64, by as many stripe slots as keep
+// the grid within 4096 workgroups; knob pairs_grid > 0 caps both dimensions.
+void stripe_grid(int64_t units, int nstripes, int& chunks, int& slots);
+
+// ---- ecamd_device.hip ----
 // Fused stage of a check or, with d_suspects, of a locate: rows [row0, row0 + nrows) of the R x K
 // matrix A as the syndrome map [A | I] through the check / locate form of the bitsliced kernel, over
 // whole tiles of every stripe.  Input j of stripe s at base + s*stripe_stride + in_off[j], fragment
@@ -142,6 +167,14 @@ int64_t check_fused(int dev, const std::vector<int>& A, int K, int row0, int nro
 int check_fused_prebuild(const std::vector<int>& A, int K, int row0, int nrows, bool locate, const char* arch,
                          const char* dir);
 
+// ---- ecamd_copy.hip: copy-through launches of the framed calls ----
+// rs_vand encode whose k data inputs are read from objects (input j of stripe s at
+// obj + s*obj_stride + j*bs) and copied into payload j while the parity is computed
+// (payload f of stripe s at payload0 + s*stripe_stride + f*frag_stride).  Objects of obj_size
+// bytes (< 0: k*bs) are zero-padded past their end (prepare_fragments_for_encode).  16-byte aligned
+// object base / stride and payloads; bs even (the object side may be read unaligned).  from > 0 (a
+// multiple of 16): only bytes [from, bs) of every payload (the rest of a partly fused encode); to > 0:
+// only bytes [from, to).
 int rs_encode_copy(int k, int m, const void* obj, int64_t obj_stride, void* payload0,
                    int64_t stripe_stride, int64_t frag_stride, int64_t bs, int nstripes,
                    void* stream, int64_t obj_size = -1, int64_t from = 0, int64_t to = -1);

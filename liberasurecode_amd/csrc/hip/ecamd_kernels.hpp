@@ -1,4 +1,4 @@
-// ecamd_kernels.hpp -- kernel argument blocks shared by ecamd_kernels.hip and ecamd_device.hip.
+// ecamd_kernels.hpp -- kernel argument blocks shared by ecamd_kernels.hip and the launch files (ecamd_launch.hpp).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

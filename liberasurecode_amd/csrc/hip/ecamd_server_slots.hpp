@@ -1,5 +1,5 @@
 // ecamd_server_slots.hpp -- which of the resident small server's two cached argument slots a request
-// takes (server_post in ecamd_device.hip).  Host logic only, no HIP: tests/c/server_slots_test.cpp
+// takes (server_post in ecamd_small.hip).  Host logic only, no HIP: tests/c/server_slots_test.cpp
 // runs it on the CPU.
 #pragma once
 #include <cstdint>

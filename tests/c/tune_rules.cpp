@@ -34,7 +34,7 @@ int g_failures = 0;
         }                                         \
     } while (0)
 
-// The return code ecamd_tune() makes of a tune_set result (ecamd_device.hip).
+// The return code ecamd_tune() makes of a tune_set result (ecamd_runtime.hip).
 int rc_of(const TuneSet& r) { return r.knob && r.stored ? 0 : kEinval; }
 
 struct KnobRecord {

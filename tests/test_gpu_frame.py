@@ -940,7 +940,7 @@ def test_frame_xor_decode_join_matches(F, k, m, hd, missing):
 
 def test_stream_contexts_bounded(F):
     """A caller that creates and destroys a stream per request (a proxy) must not grow the library's
-    per-stream contexts (side stream + events + CRC scratch, ecamd_device.hip StreamCtx): 1000 streams,
+    per-stream contexts (side stream + events + CRC scratch, ecamd_runtime.hip StreamCtx): 1000 streams,
     each used once by a Swift-shaped framed encode (1 MiB segment, k=10: bs = 104858, the payloads'
     rest forked to the side stream without checksum; CRC32 scratch with it), half destroyed through
     ecamd_stream_destroy, half behind the library's back by hipStreamDestroy.  The context count stays
