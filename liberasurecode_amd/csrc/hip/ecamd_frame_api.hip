@@ -70,12 +70,6 @@ size_t copy_lds()
     return n > 0 ? (size_t(163840) / static_cast<size_t>(n)) & ~size_t(511) : 0;
 }
 
-// Per-(device, stream) scratch for span partials (the stream's context, ecamd_internal.hpp).
-int scratch(int dev, void* stream, size_t words, uint32_t** out, int slot = 0)
-{
-    return stream_scratch(dev, stream, slot, words, out);
-}
-
 // Knob frame_tail_fork: 2 forks every padded framed encode's tail; 1 (default) only the encodes
 // without checksum whose payloads' rest is 1-4 KiB (its codec then one LDS-table launch; the headers
 // go to the side stream too): Swift segments RS 1.316 -> 1.225 ms, flat XOR 1.339 -> 1.312, 4 MiB
@@ -175,7 +169,7 @@ int run_crc(int dev, bool legacy, bool with_crc, const uint8_t* base, int64_t ss
         a.nspans = static_cast<int>(std::max<int64_t>(1, (body + span - 1) / span));
         a.c0 = zero_shift(CrcMachine(legacy), static_cast<uint64_t>(len)).apply(~0u);
         const int64_t waves = items * a.nspans;
-        rc = scratch(dev, stream, static_cast<size_t>(waves), &partial);
+        rc = stream_scratch(dev, stream, 0, static_cast<size_t>(waves), &partial);  // span partials
         if (rc) return rc;
         int wpc = g_tune.crc_wgs;
         // Measured on MI355X (C3 payloads, 3.5 GiB): B=8 at 2 workgroups/CU 6.35 TB/s, 3: 5.94,
@@ -281,6 +275,16 @@ int copy_grid(int dev, int64_t chunks_per_frag, int k, int nstripes, const CopyS
     return static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(tiles, cap)));
 }
 
+// Fragment offsets of a flat XOR encode: the k data fragments in, the m parities out.
+struct ParityOffsets {
+    std::vector<int64_t> in, out;
+    ParityOffsets(int k, int m, int64_t fs) : in(k), out(m)
+    {
+        for (int j = 0; j < k; j++) in[j] = j * fs;
+        for (int r = 0; r < m; r++) out[r] = (k + r) * fs;
+    }
+};
+
 // XOR plan of a reference operation applied in place on the payloads of every stripe.
 int xor_plan_apply(const Code& c, int op, const int* missing, int arg, uint8_t* payload0,
                    int64_t ss, int64_t fs, int64_t bs, int nstripes, void* stream,
@@ -340,6 +344,114 @@ int xor_batch_check(const Code& c, const void* base, int64_t ss, int64_t fs, int
     return 0;
 }
 
+// ---- framed encode: one record per call, one owner per step ----
+
+// One ecamd_frame_encode call, built once after validation.  `legacy` is legacy_crc() read once
+// for the whole call.
+struct EncodeJob {
+    int dev;
+    Code c;
+    bool legacy;
+    int checksum;
+    const void* obj;
+    int64_t obj_stride;
+    uint64_t obj_size;
+    uint8_t* frags;
+    int64_t ss, fs, bs;  // stripe stride, fragment stride, payload bytes
+    int nstripes;
+    void* stream;
+
+    uint8_t* payload0() const { return frags + kHeaderBytes; }
+    int nf() const { return c.k + c.m; }
+    size_t items() const { return static_cast<size_t>(nstripes) * nf(); }  // fragments of the batch
+    int64_t size() const { return static_cast<int64_t>(obj_size); }
+    int64_t r16() const { return (bs + 15) & ~int64_t(15); }
+    bool crc() const { return checksum == kChksumCrc32; }
+    bool obj_aligned() const { return aligned16(obj) && obj_stride % 16 == 0; }
+    bool fits32() const { return copy_fits32(c.k, fs, bs, size()); }
+    int64_t last_chunk() const { return size() - (c.k - 1) * bs; }  // bytes of the last data chunk
+    // the whole tiles every object chunk holds
+    int64_t cover(int64_t tile) const
+    {
+        const int64_t last = last_chunk();
+        return last > 0 ? std::min(bs, last) / tile * tile : 0;
+    }
+    HeaderArgs headers() const { return header_args(c, checksum, bs, obj_size, 0); }
+};
+
+// A strategy's "not mine": nothing is written that the next strategy does not rewrite.  Not an ECAMD
+// code, so that a codec's own ECAMD_EINVAL can pass through a strategy as the error it is.
+constexpr int kDeclined = 1;
+
+// The closing pass of every strategy: the payload CRC32s (with_crc) and the 80-byte headers.
+int finish(const EncodeJob& j, bool with_crc, void* stream)
+{
+    return run_crc(j.dev, j.legacy, with_crc, j.frags, j.ss, j.fs, kHeaderBytes, j.nf(), j.bs, j.nstripes, nullptr,
+                   j.headers(), stream);
+}
+
+// The copy-through rs_vand codec over payload bytes [from, to) (to < 0: bs), straight from the objects.
+int rs_copy(const EncodeJob& j, void* stream, int64_t from = 0, int64_t to = -1)
+{
+    return rs_encode_copy(j.c.k, j.c.m, j.obj, j.obj_stride, j.payload0(), j.ss, j.fs, j.bs, j.nstripes, stream,
+                          j.size(), from, to);
+}
+
+// prepare_fragments_for_encode for payload bytes [from, bs) (from a multiple of 16; 0 = all): the
+// streaming split kernel; frame_split_kernel, which only splits whole payloads, where 32-bit offsets
+// do not reach or knob frame_copy_stream is 0 -- whoever asks for from > 0 checks both first.
+int launch_split(const EncodeJob& j, int64_t from, void* stream)
+{
+    SplitArgs sa{static_cast<const uint8_t*>(j.obj), j.obj_stride, j.size(), j.frags, j.ss, j.fs, j.bs, j.c.k,
+                 j.nstripes, j.obj_aligned() && j.bs % 16 == 0 ? 1 : 0, from};
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (j.fits32() && g_tune.frame_copy_stream != 0) {
+        const CopyShape cs = copy_shape(j.bs);
+        const dim3 grid(copy_grid(j.dev, (j.r16() - from) / 16, j.c.k, j.nstripes, cs)), block(cs.threads);
+        const bool dpp = g_tune.frame_copy_dpp != 0;
+        if (cs.u == 1)
+            hipLaunchKernelGGL((dpp ? frame_split_stream_kernel<1, true> : frame_split_stream_kernel<1, false>), grid,
+                               block, copy_lds(), st, sa);
+        else
+            hipLaunchKernelGGL((dpp ? frame_split_stream_kernel<4, true> : frame_split_stream_kernel<4, false>), grid,
+                               block, copy_lds(), st, sa);
+    } else {
+        if (from) return dev_fail(ECAMD_EHIP, "framed encode: a partial split without the streaming kernel");
+        hipLaunchKernelGGL(frame_split_kernel, dim3(grid_for(j.dev, ((j.bs + 15) / 16) * j.c.k * j.nstripes)),
+                           dim3(256), 0, st, sa);
+    }
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// xor_code_encode accumulates into zeroed parity (src/builtin/xor_codes/xor_code.c:180-191): parity r =
+// XOR of the data fragments in masks[r], here over payload bytes [from, bs).
+int xor_parity(const EncodeJob& j, const uint32_t* masks, int64_t from, void* stream)
+{
+    const ParityOffsets off(j.c.k, j.c.m, j.fs);
+    uint8_t* p = j.payload0() + from;
+    return ecamd_xor_apply_strided(masks, j.c.m, j.c.k, p, j.ss, off.in.data(), p, j.ss, off.out.data(), j.bs - from,
+                                   j.nstripes, stream);
+}
+
+// Side work beside main work: the side work is enqueued first, on the side stream (ordered after
+// everything on the job's stream so far); the main work, on the job's stream, only if the side work
+// returned 0; then the join.  rc: the fork's, else the side work's, else the main work's; rj: the
+// join's (0 when the fork failed).  What rc and rj mean is each caller's own rule.
+struct Forked {
+    int rc, rj;
+};
+template <class Side, class Main>
+Forked forked(const EncodeJob& j, Side side_work, Main main_work)
+{
+    void* side = nullptr;
+    int rc = side_fork(j.dev, j.stream, &side);
+    if (rc) return {rc, 0};
+    rc = side_work(side);
+    if (rc == 0) rc = main_work();
+    return {rc, side_join(j.dev, j.stream)};
+}
+
 // ---- fused CHKSUM_CRC32 framed encode (hip/ecamd_frame_fused.hip) ----
 
 std::map<std::pair<int, int>, const uint32_t*> g_fused_images;  // (dev, legacy + 2 * mb) -> device image
@@ -363,10 +475,6 @@ int fused_image(int dev, bool legacy, int mb, const uint32_t** out, int tile = 8
     return 0;
 }
 
-// The object-filling rs_vand encode with CRC32 checksums as ONE codec launch that also folds the
-// payload checksums (q ranges per payload), then crc_finalize_kernel over the ranges and the
-// headers.  ECAMD_EINVAL (nothing launched) when the shape does not fit: the caller runs the
-// copy-through encode + separate CRC pass instead.
 // Ranges per payload for the fused CRC kernels: enough work units (stripes x ranges) to fill the
 // chip, each a long sequential run of whole tiles.
 // q divides `tiles`: the smallest divisor that gives per_cu units per CU, else one tile per unit (odd
@@ -385,15 +493,15 @@ int fused_ranges(int dev, int64_t tiles, int nstripes, int default_per_cu)
 // crc_finalize_kernel over the q ranges of every payload of the batch and the 80-byte headers.
 // cover < bs: the ranges span the payloads' first `cover` bytes and tail_crc[item] holds the CRC32
 // of the rest (bs - cover bytes), folded in after them.
-int finalize_ranges(int dev, const Code& c, bool legacy, uint64_t obj_size, uint8_t* frags, int64_t ss,
-                    int64_t fs, int64_t bs, int nstripes, const uint32_t* partial, int q, void* stream,
-                    int64_t cover = -1, const uint32_t* tail_crc = nullptr)
+int finalize_ranges(const EncodeJob& j, const uint32_t* partial, int q, int64_t cover = -1,
+                    const uint32_t* tail_crc = nullptr)
 {
-    const int nf = c.k + c.m;
+    const bool legacy = j.legacy;
+    const int64_t bs = j.bs;
     if (cover < 0) cover = bs;
     const int J = static_cast<int>(cover / q / 1024);  // KiB per range
     const DevImage* di = nullptr;
-    int rc = image(dev, legacy, 5, J, 8, false, &di);
+    int rc = image(j.dev, legacy, 5, J, 8, false, &di);
     if (rc) return rc;
     CrcArgs a{};
     if (cover < bs) {
@@ -404,14 +512,14 @@ int finalize_ranges(int dev, const Code& c, bool legacy, uint64_t obj_size, uint
         a.tail_crc = tail_crc;
         a.tail_c0 = sh.apply(~0u);
     }
-    a.base = frags;
-    a.stripe_stride = ss;
-    a.frag_stride = fs;
+    a.base = j.frags;
+    a.stripe_stride = j.ss;
+    a.frag_stride = j.fs;
     a.payload_off = kHeaderBytes;
     a.len = cover;  // (no byte steps: the ranges end exactly at `cover`)
     a.body = cover;
-    a.items = static_cast<int64_t>(nstripes) * nf;
-    a.nfrag = nf;
+    a.items = static_cast<int64_t>(j.nstripes) * j.nf();
+    a.nfrag = j.nf();
     a.nspans = q;
     a.J = J;
     a.legacy = legacy ? 1 : 0;
@@ -419,8 +527,7 @@ int finalize_ranges(int dev, const Code& c, bool legacy, uint64_t obj_size, uint
     a.span_off = static_cast<uint32_t>(di->img.span_off);
     a.t_off = static_cast<uint32_t>(di->img.t_off);
     hipLaunchKernelGGL(crc_finalize_kernel, dim3(static_cast<unsigned>((a.items + 127) / 128)), dim3(128), 0,
-                       static_cast<hipStream_t>(stream), a, di->d, partial, nullptr,
-                       header_args(c, kChksumCrc32, bs, obj_size, 0));
+                       static_cast<hipStream_t>(j.stream), a, di->d, partial, nullptr, j.headers());
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -446,93 +553,88 @@ int crc_wave_groups(int64_t tps)
         if (tps % d == 0) g = d;
     return g;
 }
-int crc_wave_combine(int dev, bool legacy, const uint32_t* tiles, int64_t items, int nf, int64_t tps, int g,
-                     uint32_t* partial, void* stream)
+int crc_wave_combine(const EncodeJob& j, const uint32_t* tiles, int64_t tps, int g, uint32_t* partial)
 {
     const DevImage* di = nullptr;
-    int rc = image(dev, legacy, 5, 4, 8, false, &di);  // span tables: A^4096
+    int rc = image(j.dev, j.legacy, 5, 4, 8, false, &di);  // span tables: A^4096
     if (rc) return rc;
+    const int64_t items = static_cast<int64_t>(j.nstripes) * j.nf();
     const int64_t n = items * (tps / g);
     hipLaunchKernelGGL(crc_combine_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), tiles, partial, di->d + di->img.span_off, items, nf,
+                       static_cast<hipStream_t>(j.stream), tiles, partial, di->d + di->img.span_off, items, j.nf(),
                        static_cast<int>(tps), g);
     HIP_TRY(hipGetLastError());
     return 0;
+}
+// Knob frame_crc_wave_strict: the one-wave form (wf) declining is an error, not a fallback.
+int wave_strict(int rc, int wf)
+{
+    return rc == ECAMD_EINVAL && wf && g_tune.frame_crc_wave_strict
+               ? dev_fail(ECAMD_EHIP, "framed encode: the one-wave crc form declined")
+               : rc;
+}
+
+// The bitsliced crc variant's form over the first `span` bytes of every payload: the crc_pos flags
+// word rs_ / xor_encode_copy_crc_bs take, its tile, the whole tiles it covers as q ranges of g-tile
+// groups, and its image (fused_image's key).  wf: crc_wave_form's flags, 0 = 16 KiB tiles.
+struct CrcBsForm {
+    int flags;
+    int64_t tile, cover, tps;  // bytes per tile, whole tiles' bytes, tiles per payload
+    int g, q;
+    int mb, step, npos;
+    bool nib;
+    int image(const EncodeJob& j, const uint32_t** out) const
+    {
+        return fused_image(j.dev, j.legacy, mb, out, step, npos, nib);
+    }
+};
+CrcBsForm crc_bs_form(const EncodeJob& j, int wf, int64_t span)
+{
+    if (wf) {
+        const int64_t tps = span / 4096;
+        const int g = crc_wave_groups(tps);
+        return {wf, 4096, tps * 4096, tps, g, static_cast<int>(tps / g), crc_wave_mb(wf), 1024, wf & 7, false};
+    }
+    const int64_t tps = span / 16384;
+    // one 16 KiB tile per work unit at C3 (64 units per CU, one per workgroup): the dispatcher
+    // balances them (32 / 16 per CU measured 3 / 6% slower, profiles/r03_fused_sweep_pos.log);
+    // maps of 5-8 outputs fold every tile on its own (one range per tile)
+    const int q = j.c.m > 4 ? static_cast<int>(tps) : fused_ranges(j.dev, tps, j.nstripes, 64);
+    // maps of 5-8 outputs always fold with the lane-shift tables (bitslice.cpp fold_each)
+    const bool lane = j.c.m > 4 || g_tune.frame_crc_lane != 0;
+    int npos = g_tune.frame_crc_pos;
+    if (npos <= 0) npos = lane && j.c.m <= 4 ? 1 : 2;
+    const bool nib = g_tune.frame_crc_bs_nib > 0;
+    return {npos | (lane ? 8 : 0) | (nib ? 16 : 0), 16384, tps * 16384, tps, 1, q, 4, 4096, npos, nib};
 }
 
 // The same framed encode on the bitsliced kernel's crc variant (no codec tables: the LDS serves
 // only the CRC lookups) for maps of up to 4 outputs over whole 16 KiB tiles.  ECAMD_EINVAL when it
 // does not apply or its kernel is still compiling (knob bitslice 1): the caller runs the LDS-table
 // fused kernel instead.
-int encode_crc_bitsliced(int dev, const Code& c, bool legacy, const void* obj, int64_t obj_stride,
-                         uint64_t obj_size, uint8_t* frags, int64_t ss, int64_t fs, int64_t bs,
-                         int nstripes, void* stream)
+int encode_crc_bitsliced(const EncodeJob& j)
 {
-    if (g_tune.frame_crc_bs == 0 || c.m > 8 || nstripes <= 0) return ECAMD_EINVAL;
-    if (const int wf = crc_wave_form(c, bs)) {
-        const int nf = c.k + c.m;
-        const int64_t tps = bs / 4096;
-        const int g = crc_wave_groups(tps);
-        uint32_t *tiles = nullptr, *partial = nullptr;
-        int rc = scratch(dev, stream, static_cast<size_t>(nstripes) * static_cast<size_t>(tps) * nf, &tiles, 3);
-        if (rc || (rc = scratch(dev, stream, static_cast<size_t>(nstripes) * nf * static_cast<size_t>(tps / g),
-                                &partial)))
-            return rc;
-        const uint32_t* img = nullptr;
-        if ((rc = fused_image(dev, legacy, crc_wave_mb(wf), &img, 1024, wf & 7, false))) return rc;
-        if ((rc = rs_encode_copy_crc_bs(c.k, c.m, obj, obj_stride, frags + kHeaderBytes, ss, fs, bs, nstripes, img,
-                                        tiles, 0, stream, wf)))
-            return rc == ECAMD_EINVAL && g_tune.frame_crc_wave_strict
-                       ? dev_fail(ECAMD_EHIP, "framed encode: the one-wave crc form declined")
-                       : rc;
-        if ((rc = crc_wave_combine(dev, legacy, tiles, static_cast<int64_t>(nstripes) * nf, nf, tps, g, partial,
-                                   stream)))
-            return rc;
-        return finalize_ranges(dev, c, legacy, obj_size, frags, ss, fs, bs, nstripes, partial,
-                               static_cast<int>(tps / g), stream);
-    }
-    if (bs % 16384) return ECAMD_EINVAL;
-    // one 16 KiB tile per work unit at C3 (64 units per CU, one per workgroup): the dispatcher
-    // balances them (32 / 16 per CU measured 3 / 6% slower, profiles/r03_fused_sweep_pos.log);
-    // maps of 5-8 outputs fold every tile on its own (one range per tile)
-    const int q = c.m > 4 ? static_cast<int>(bs / 16384) : fused_ranges(dev, bs / 16384, nstripes, 64);
-    uint32_t* partial = nullptr;
-    int rc = scratch(dev, stream, static_cast<size_t>(nstripes) * (c.k + c.m) * q, &partial);
-    if (rc) return rc;
+    const Code& c = j.c;
+    if (g_tune.frame_crc_bs == 0 || c.m > 8 || j.nstripes <= 0) return ECAMD_EINVAL;
+    const int wf = crc_wave_form(c, j.bs);
+    const CrcBsForm f = crc_bs_form(j, wf, j.bs);
+    if (f.cover != j.bs) return ECAMD_EINVAL;  // whole tiles only
+    uint32_t *tiles = nullptr, *partial = nullptr;
+    int rc;
+    if (wf && (rc = stream_scratch(j.dev, j.stream, 3, j.items() * static_cast<size_t>(f.tps), &tiles))) return rc;
+    if ((rc = stream_scratch(j.dev, j.stream, 0, j.items() * f.q, &partial))) return rc;
     const uint32_t* img = nullptr;
-    // maps of 5-8 outputs always fold with the lane-shift tables (bitslice.cpp fold_each)
-    const bool lane = c.m > 4 || g_tune.frame_crc_lane != 0;
-    int npos = g_tune.frame_crc_pos;
-    if (npos <= 0) npos = lane && c.m <= 4 ? 1 : 2;
-    const bool nib = g_tune.frame_crc_bs_nib > 0;
-    if ((rc = fused_image(dev, legacy, 4, &img, 4096, npos, nib))) return rc;
-    rc = rs_encode_copy_crc_bs(c.k, c.m, obj, obj_stride, frags + kHeaderBytes, ss, fs, bs, nstripes, img,
-                               partial, q, stream, npos | (lane ? 8 : 0) | (nib ? 16 : 0));
-    if (rc) return rc;
-    return finalize_ranges(dev, c, legacy, obj_size, frags, ss, fs, bs, nstripes, partial, q, stream);
+    if ((rc = f.image(j, &img))) return rc;
+    // (one-wave form: per-tile partials and no ranges in the launch; combined below)
+    if ((rc = wave_strict(rs_encode_copy_crc_bs(c.k, c.m, j.obj, j.obj_stride, j.payload0(), j.ss, j.fs, j.bs,
+                                                j.nstripes, img, wf ? tiles : partial, wf ? 0 : f.q, j.stream,
+                                                f.flags),
+                          wf)))
+        return rc;
+    if (wf && (rc = crc_wave_combine(j, tiles, f.tps, f.g, partial))) return rc;
+    return finalize_ranges(j, partial, f.q);
 }
 
-// prepare_fragments_for_encode for payload bytes [from, bs) only (from a multiple of 16; 0 = all):
-// the streaming split kernel (callers check copy_fits32).
-int split_range(int dev, int k, const void* obj, int64_t obj_stride, uint64_t obj_size, uint8_t* frags, int64_t ss,
-                int64_t fs, int64_t bs, int nstripes, int64_t from, void* stream)
-{
-    const int64_t r16 = (bs + 15) & ~int64_t(15);
-    SplitArgs sa{static_cast<const uint8_t*>(obj), obj_stride, static_cast<int64_t>(obj_size), frags, ss, fs, bs,
-                 k, nstripes, 0, from};
-    const CopyShape cs = copy_shape(bs);
-    const dim3 grid(copy_grid(dev, (r16 - from) / 16, k, nstripes, cs)), block(cs.threads);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const bool dpp = g_tune.frame_copy_dpp != 0;
-    if (cs.u == 1)
-        hipLaunchKernelGGL((dpp ? frame_split_stream_kernel<1, true> : frame_split_stream_kernel<1, false>), grid, block,
-                           copy_lds(), st, sa);
-    else
-        hipLaunchKernelGGL((dpp ? frame_split_stream_kernel<4, true> : frame_split_stream_kernel<4, false>), grid, block,
-                           copy_lds(), st, sa);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
 
 // The rest [from, bs) of every payload of an RS copy-through encode whose first `from` bytes are
 // done (bytes [0, from) of the data payloads written): a streaming split copies the object chunks'
@@ -547,28 +649,22 @@ int split_range(int dev, int k, const void* obj, int64_t obj_stride, uint64_t ob
 // crc variant leaves one on Swift's segments) go first through the copy-through launch of exactly
 // that range, so the split and the re-encoded tiles shrink to the last partial tile (knob
 // frame_tail_tiles, default on).
-int encode_tail(int dev, const Code& c, const void* obj, int64_t obj_stride, uint64_t obj_size, uint8_t* frags,
-                int64_t ss, int64_t fs, int64_t bs, int nstripes, int64_t from, void* stream)
+int encode_tail(const EncodeJob& j, int64_t from, void* stream)
 {
     constexpr int64_t kTile = 4096;
-    if (g_tune.frame_tail_bs == 0 || from <= 0 || from % 16 || from >= bs ||
-        !copy_fits32(c.k, fs, bs, static_cast<int64_t>(obj_size)) || g_tune.frame_copy_stream == 0)
+    if (g_tune.frame_tail_bs == 0 || from <= 0 || from % 16 || from >= j.bs || !j.fits32() ||
+        g_tune.frame_copy_stream == 0)
         return ECAMD_EINVAL;
-    const int64_t last = static_cast<int64_t>(obj_size) - (c.k - 1) * bs;
-    const int64_t c4 = last > 0 ? std::min(bs, last) / kTile * kTile : 0;  // whole 4 KiB tiles of every chunk
-    const int64_t r16 = (bs + 15) & ~int64_t(15);
-    const int64_t mid = g_tune.frame_tail_tiles != 0 && c4 > from && c4 < bs ? c4 : from;
-    const int64_t n = (r16 - mid + kTile - 1) / kTile;
-    const int64_t t0 = r16 - n * kTile;
+    const int64_t c4 = j.cover(kTile);
+    const int64_t mid = g_tune.frame_tail_tiles != 0 && c4 > from && c4 < j.bs ? c4 : from;
+    const int64_t n = (j.r16() - mid + kTile - 1) / kTile;
+    const int64_t t0 = j.r16() - n * kTile;
     if (t0 < 0) return ECAMD_EINVAL;
     int rc;
-    if (mid > from && (rc = rs_encode_copy(c.k, c.m, obj, obj_stride, frags + kHeaderBytes, ss, fs, bs, nstripes,
-                                           stream, static_cast<int64_t>(obj_size), from, mid)))
+    if (mid > from && (rc = rs_copy(j, stream, from, mid)))
         return rc == ECAMD_EINVAL ? dev_fail(ECAMD_EHIP, "framed encode: tail tiles failed") : rc;
-    from = mid;
-    rc = split_range(dev, c.k, obj, obj_stride, obj_size, frags, ss, fs, bs, nstripes, from, stream);
-    if (rc) return rc;
-    rc = ecamd_rs_encode(c.k, c.m, frags + kHeaderBytes + t0, ss, fs, n * kTile, nstripes, stream);
+    if ((rc = launch_split(j, mid, stream))) return rc;
+    rc = ecamd_rs_encode(j.c.k, j.c.m, j.payload0() + t0, j.ss, j.fs, n * kTile, j.nstripes, stream);
     return rc == ECAMD_EINVAL ? dev_fail(ECAMD_EHIP, "framed encode: tail encode failed") : rc;
 }
 
@@ -579,115 +675,83 @@ int encode_tail(int dev, const Code& c, const void* obj, int64_t obj_stride, uin
 // own (run_crc), and the finalize folding each tail into its payload's ranges:
 // r0(X || Y) = A^|Y| r0(X) ^ r0(Y).  ECAMD_EINVAL, nothing launched, when it does not apply or the
 // bitsliced kernel is still compiling: the caller runs the copy-through encode + CRC pass.
-int encode_crc_cover(int dev, const Code& c, bool legacy, const void* obj, int64_t obj_stride,
-                     uint64_t obj_size, uint8_t* frags, int64_t ss, int64_t fs, int64_t bs, int nstripes,
-                     void* stream)
+int encode_crc_cover(const EncodeJob& j)
 {
+    const Code& c = j.c;
     const bool xorc = c.backend == kBackendXor;
-    if (g_tune.frame_crc_cover == 0 || g_tune.frame_crc_bs == 0 || g_tune.frame_crc_fused == 0 ||
-        c.m > 8 || bs % 2 || nstripes <= 0 || (xorc && !copy_fits32(c.k, fs, bs, static_cast<int64_t>(obj_size))))
+    if (g_tune.frame_crc_cover == 0 || g_tune.frame_crc_bs == 0 || g_tune.frame_crc_fused == 0 || c.m > 8 ||
+        j.bs % 2 || j.nstripes <= 0 || (xorc && !j.fits32()))
         return ECAMD_EINVAL;
-    const int64_t last = static_cast<int64_t>(obj_size) - (c.k - 1) * bs;  // bytes of the last data chunk
     // the one-wave crc form covers whole 4 KiB tiles, the 16 KiB-tile crc variant whole 16 KiB tiles
-    const int wf = last > 0 ? crc_wave_form(c, std::min(bs, last) / 4096 * 4096) : 0;
-    const int64_t kTile = wf ? 4096 : 16384;
-    const int64_t cover = last > 0 ? std::min(bs, last) / kTile * kTile : 0;
-    if (last <= 0 || cover < kTile) return ECAMD_EINVAL;
-    const int64_t tail = bs - cover;
-    const int nf = c.k + c.m;
-    const int64_t tps = cover / kTile;
-    const int g = wf ? crc_wave_groups(tps) : 1;
-    const int q = wf ? static_cast<int>(tps / g)
-                     : c.m > 4 ? static_cast<int>(tps) : fused_ranges(dev, tps, nstripes, 64);
+    const int wf = crc_wave_form(c, j.cover(4096));
+    const CrcBsForm form = crc_bs_form(j, wf, j.cover(4096));
+    const int64_t cover = form.cover, tps = form.tps;
+    if (cover < form.tile) return ECAMD_EINVAL;
+    const int64_t tail = j.bs - cover;
+    const int g = form.g, q = form.q;
     uint32_t *partial = nullptr, *tail_crc = nullptr, *tiles = nullptr;
-    int rc = scratch(dev, stream, static_cast<size_t>(nstripes) * nf * q, &partial, 1);
+    int rc = stream_scratch(j.dev, j.stream, 1, j.items() * q, &partial);
     if (rc) return rc;
-    if (tail && (rc = scratch(dev, stream, static_cast<size_t>(nstripes) * nf, &tail_crc, 2))) return rc;
-    if (wf && (rc = scratch(dev, stream, static_cast<size_t>(nstripes) * static_cast<size_t>(tps) * nf, &tiles, 3)))
-        return rc;
+    if (tail && (rc = stream_scratch(j.dev, j.stream, 2, j.items(), &tail_crc))) return rc;
+    if (wf && (rc = stream_scratch(j.dev, j.stream, 3, j.items() * static_cast<size_t>(tps), &tiles))) return rc;
     const uint32_t* img = nullptr;
-    const bool lane = c.m > 4 || g_tune.frame_crc_lane != 0;
-    int npos = g_tune.frame_crc_pos;
-    if (npos <= 0) npos = lane && c.m <= 4 ? 1 : 2;
-    const bool nib = g_tune.frame_crc_bs_nib > 0;
-    if ((rc = wf ? fused_image(dev, legacy, crc_wave_mb(wf), &img, 1024, wf & 7, false)
-                 : fused_image(dev, legacy, 4, &img, 4096, npos, nib)))
-        return rc;
+    if ((rc = form.image(j, &img))) return rc;
     unsigned pb[32], db[32];
     if (xorc) ecamd_xor_code_tables(c.k, c.m, c.hd, pb, db);
-    const int pos = wf ? wf : npos | (lane ? 8 : 0) | (nib ? 16 : 0);
     uint32_t* out = wf ? tiles : partial;  // (one-wave form: per-tile partials, combined below)
     auto whole = [&] {  // the whole tiles [0, cover): codec + copy + CRC partials in one launch
-        const int r = xorc ? xor_encode_copy_crc_bs(pb, c.k, c.m, obj, obj_stride, frags + kHeaderBytes, ss, fs, bs,
-                                                    nstripes, img, out, q, stream, pos, cover)
-                           : rs_encode_copy_crc_bs(c.k, c.m, obj, obj_stride, frags + kHeaderBytes, ss, fs, bs, nstripes,
-                                                   img, out, q, stream, pos, cover);
-        return r == ECAMD_EINVAL && wf && g_tune.frame_crc_wave_strict
-                   ? dev_fail(ECAMD_EHIP, "framed encode: the one-wave crc form declined")
-                   : r;
+        return wave_strict(xorc ? xor_encode_copy_crc_bs(pb, c.k, c.m, j.obj, j.obj_stride, j.payload0(), j.ss, j.fs,
+                                                         j.bs, j.nstripes, img, out, q, j.stream, form.flags, cover)
+                                : rs_encode_copy_crc_bs(c.k, c.m, j.obj, j.obj_stride, j.payload0(), j.ss, j.fs, j.bs,
+                                                        j.nstripes, img, out, q, j.stream, form.flags, cover),
+                           wf);
     };
     // the payloads' rest [cover, bs): codec, then the CRC32 of that range on its own; `exact`: no byte
     // below cover is touched (the side stream runs it beside whole())
     auto rest = [&](void* st, bool exact) {
         int r;
         if (xorc) {  // the data payloads' rest by the split, then the XOR of that range
-            r = split_range(dev, c.k, obj, obj_stride, obj_size, frags, ss, fs, bs, nstripes, cover, st);
-            if (r == 0) {
-                std::vector<int64_t> in_off(c.k), out_off(c.m);
-                for (int j = 0; j < c.k; j++) in_off[j] = j * fs;
-                for (int o = 0; o < c.m; o++) out_off[o] = (c.k + o) * fs;
-                uint8_t* pc = frags + kHeaderBytes + cover;
-                r = ecamd_xor_apply_strided(pb, c.m, c.k, pc, ss, in_off.data(), pc, ss, out_off.data(), bs - cover,
-                                            nstripes, st);
-            }
+            if ((r = launch_split(j, cover, st)) == 0) r = xor_parity(j, pb, cover, st);
         } else {
             // encode_tail re-encodes whole 4 KiB tiles reaching below cover from the payloads: only
             // after whole() on the same stream
-            r = exact ? ECAMD_EINVAL : encode_tail(dev, c, obj, obj_stride, obj_size, frags, ss, fs, bs, nstripes, cover, st);
-            if (r == ECAMD_EINVAL)
-                r = rs_encode_copy(c.k, c.m, obj, obj_stride, frags + kHeaderBytes, ss, fs, bs, nstripes, st,
-                                   static_cast<int64_t>(obj_size), cover);
+            r = exact ? ECAMD_EINVAL : encode_tail(j, cover, st);
+            if (r == ECAMD_EINVAL) r = rs_copy(j, st, cover);
         }
         if (r) return r == ECAMD_EINVAL ? dev_fail(ECAMD_EHIP, "framed encode: tail codec failed") : r;
         HeaderArgs none{};
-        if ((r = run_crc(dev, legacy, true, frags, ss, fs, kHeaderBytes + cover, nf, tail, nstripes, tail_crc, none,
-                         st)))
+        if ((r = run_crc(j.dev, j.legacy, true, j.frags, j.ss, j.fs, kHeaderBytes + cover, j.nf(), tail, j.nstripes,
+                         tail_crc, none, st)))
             return r == ECAMD_EINVAL ? dev_fail(ECAMD_EHIP, "framed encode: tail CRC failed") : r;
         return 0;
     };
     if (fork_tail(tail, true)) {
-        void* side = nullptr;
-        if ((rc = side_fork(dev, stream, &side))) return rc;
-        rc = rest(side, true);
         // whole() may decline (ECAMD_EINVAL: the kernel is still compiling): the caller's fallback then
         // rewrites every payload after the tails (joined first), byte-identically
-        if (rc == 0) rc = whole();
-        const int rj = side_join(dev, stream);
-        if (rc || rj) return rc ? rc : rj;
+        const Forked f = forked(j, [&](void* side) { return rest(side, true); }, whole);
+        if (f.rc || f.rj) return f.rc ? f.rc : f.rj;
     } else {
         if ((rc = whole())) return rc;
         // from here on a failure is an error, not a fallback: part of the payloads is written
-        if (tail && (rc = rest(stream, false))) return rc;
+        if (tail && (rc = rest(j.stream, false))) return rc;
     }
-    if (wf && (rc = crc_wave_combine(dev, legacy, tiles, static_cast<int64_t>(nstripes) * nf, nf, tps, g, partial,
-                                     stream)))
-        return rc;
-    return finalize_ranges(dev, c, legacy, obj_size, frags, ss, fs, bs, nstripes, partial, q, stream, cover,
-                           tail_crc);
+    if (wf && (rc = crc_wave_combine(j, tiles, tps, g, partial))) return rc;
+    return finalize_ranges(j, partial, q, cover, tail_crc);
 }
 
-int encode_crc_fused(int dev, const Code& c, bool legacy, const void* obj, int64_t obj_stride,
-                     uint64_t obj_size, uint8_t* frags, int64_t ss, int64_t fs, int64_t bs,
-                     int nstripes, void* stream)
+// The object-filling rs_vand encode with CRC32 checksums as ONE codec launch that also folds the
+// payload checksums (q ranges per payload), then crc_finalize_kernel over the ranges and the
+// headers.  ECAMD_EINVAL (nothing launched) when the shape does not fit: the caller runs the
+// copy-through encode + separate CRC pass instead.
+int encode_crc_fused(const EncodeJob& j)
 {
-    if (g_tune.frame_crc_fused == 0 || bs % 8192 || nstripes <= 0) return ECAMD_EINVAL;
-    int rc = encode_crc_bitsliced(dev, c, legacy, obj, obj_stride, obj_size, frags, ss, fs, bs, nstripes, stream);
+    const Code& c = j.c;
+    if (g_tune.frame_crc_fused == 0 || j.bs % 8192 || j.nstripes <= 0) return ECAMD_EINVAL;
+    int rc = encode_crc_bitsliced(j);
     if (rc != ECAMD_EINVAL) return rc;
-    const int q = fused_ranges(dev, bs / 8192, nstripes, 4);
-    const int nf = c.k + c.m;
+    const int q = fused_ranges(j.dev, j.bs / 8192, j.nstripes, 4);
     uint32_t* partial = nullptr;
-    rc = scratch(dev, stream, static_cast<size_t>(nstripes) * nf * q, &partial);
-    if (rc) return rc;
+    if ((rc = stream_scratch(j.dev, j.stream, 0, j.items() * q, &partial))) return rc;
     const uint32_t* img = nullptr;
     // all-byte piece tables (16 KiB) measured 4% faster than byte + nibble (MB = 1, 5.5 KiB) in the
     // fused kernel, where the LDS also serves the codec; MB = 1 when the larger image does not fit
@@ -695,11 +759,196 @@ int encode_crc_fused(int dev, const Code& c, bool legacy, const void* obj, int64
     const bool nib = g_tune.frame_crc_nib != 0;
     int mb = g_tune.frame_crc_mb == 1 ? 1 : 4;
     if (mb == 4 && fused_crc_lds(c.k, c.m, 4, nib) > static_cast<size_t>(kLdsBytes)) mb = 1;
-    if ((rc = fused_image(dev, legacy, mb, &img))) return rc;
-    rc = rs_encode_copy_crc(c.k, c.m, obj, obj_stride, frags + kHeaderBytes, ss, fs, bs, nstripes, img,
-                            partial, q, stream, mb, nib);
+    if ((rc = fused_image(j.dev, j.legacy, mb, &img))) return rc;
+    if ((rc = rs_encode_copy_crc(c.k, c.m, j.obj, j.obj_stride, j.payload0(), j.ss, j.fs, j.bs, j.nstripes, img,
+                                 partial, q, j.stream, mb, nib)))
+        return rc;
+    return finalize_ranges(j, partial, q);
+}
+
+// ---- the strategies of ecamd_frame_encode, in the order it tries them ----
+
+// rs_vand, the object fills the k payloads exactly (no padding): one launch reads it, copies the
+// data into the payloads and writes the parity (10 MiB read + 14 MiB written per C3 stripe instead
+// of a separate split pass) -- with CRC32 checksums, the same launch also folds the payload
+// checksums (no re-read of the 14 MiB).  A codec failure is returned, ECAMD_EINVAL included: no
+// split fallback.
+int encode_rs_exact(const EncodeJob& j)
+{
+    if (j.c.backend != kBackendRs || !j.obj_aligned() || j.bs % 16 || j.size() != j.c.k * j.bs ||
+        g_tune.frame_unfused != 0)
+        return kDeclined;
+    int rc;
+    if (j.crc() && ((rc = encode_crc_fused(j)) != ECAMD_EINVAL || (rc = encode_crc_cover(j)) != ECAMD_EINVAL))
+        return rc;
+    if ((rc = rs_copy(j, j.stream))) return rc;
+    return finish(j, j.crc(), j.stream);
+}
+
+// rs_vand, objects that do not fill the payloads exactly (any size: Swift's 1 MiB segments give
+// bs = 104858): the same copy-through launch reads each chunk j*bs of the object with unaligned
+// loads and reads zeros past the object's end, so no split pass either; with CRC32 checksums the
+// whole tiles also fold them in the same launch (encode_crc_cover).  A codec failure is returned,
+// ECAMD_EINVAL included: no split fallback.
+int encode_rs_padded(const EncodeJob& j)
+{
+    if (j.c.backend != kBackendRs || !j.obj_aligned() || g_tune.frame_unfused != 0 || g_tune.frame_copy_padded == 0)
+        return kDeclined;
+    int rc;
+    if (j.crc() && (rc = encode_crc_cover(j)) != ECAMD_EINVAL) return rc;
+    // the whole 4 KiB tiles every payload holds on the copy-through launch; the rest by the
+    // copy-through codec of exactly [cover, bs) on the side stream beside it (knob
+    // frame_tail_fork), or after it by encode_tail (split + plain encode of the payloads' last tiles)
+    const int64_t cover = j.cover(4096);
+    if (cover > 0 && fork_tail(j.bs - cover, j.crc())) {
+        const bool heads = !j.crc();  // no checksum: the headers read no payload byte
+        const Forked f = forked(
+            j,
+            [&](void* side) {  // the rest [cover, bs), from the objects (exact range), beside the whole tiles
+                const int r = rs_copy(j, side, cover);
+                return r == 0 && heads ? finish(j, false, side) : r;
+            },
+            [&] { return rs_copy(j, j.stream, 0, cover); });
+        if (f.rc || f.rj || heads) return f.rc ? f.rc : f.rj;
+    } else if (cover > 0 && cover < j.bs && g_tune.frame_tail_bs != 0) {
+        if ((rc = rs_copy(j, j.stream, 0, cover))) return rc;
+        if ((rc = encode_tail(j, cover, j.stream)) == ECAMD_EINVAL) rc = rs_copy(j, j.stream, cover);
+        if (rc) return rc;
+    } else if ((rc = rs_copy(j, j.stream))) {
+        return rc;
+    }
+    return finish(j, j.crc(), j.stream);
+}
+
+// flat XOR, copy-through (round 4): the whole 4 KiB tiles every object chunk holds in one launch
+// that reads the chunks, writes the data payloads and the parity; the payloads' rest by the
+// streaming split + the XOR of that range; then the CRC pass and headers.  Against split + XOR it
+// moves 26 instead of 36 payload-sized units of HBM traffic per stripe at (10,6).  Only a codec's
+// ECAMD_EINVAL declines (the split path rewrites every byte, the forked tails included); a failed
+// join is returned at once.
+int encode_xor_copy(const EncodeJob& j)
+{
+    const Code& c = j.c;
+    if (c.backend != kBackendXor || !j.obj_aligned() || g_tune.frame_unfused != 0 || g_tune.frame_xor_copy == 0 ||
+        g_tune.frame_copy_stream == 0 || !j.fits32())
+        return kDeclined;
+    int rc;
+    // the checksums folded into the codec launch, as for RS
+    if (j.crc() && (rc = encode_crc_cover(j)) != ECAMD_EINVAL) return rc;
+    const int64_t cover = j.cover(4096);
+    unsigned pb[32], db[32];
+    ecamd_xor_code_tables(c.k, c.m, c.hd, pb, db);
+    auto whole = [&] {
+        return xor_encode_copy(pb, c.k, c.m, j.obj, j.obj_stride, j.payload0(), j.ss, j.fs, j.bs, cover, j.nstripes,
+                               j.stream);
+    };
+    // the payloads' rest [cover, bs): split, then the XOR of that range (bytes disjoint from the
+    // copy-through launch: on the side stream beside it, knob frame_tail_fork)
+    auto rest = [&](void* st) {
+        int r = launch_split(j, cover, st);
+        if (r == 0) r = xor_parity(j, pb, cover, st);
+        return r == ECAMD_EINVAL ? dev_fail(ECAMD_EHIP, "framed xor encode: tail failed") : r;
+    };
+    if (cover > 0 && fork_tail(j.bs - cover, j.crc())) {
+        const bool heads = !j.crc();  // no checksum: the headers read no payload byte
+        const Forked f = forked(
+            j,
+            [&](void* side) {
+                const int r = rest(side);
+                return r == 0 && heads ? finish(j, false, side) : r;
+            },
+            whole);
+        if (f.rj) return f.rj;
+        if (f.rc == 0 && heads) return 0;
+        rc = f.rc;
+    } else {
+        rc = cover > 0 ? whole() : ECAMD_EINVAL;
+        // from here on a failure is an error: part of the payloads is written
+        if (rc == 0 && cover < j.bs && (rc = rest(j.stream))) return rc;
+    }
+    if (rc == 0) return finish(j, j.crc(), j.stream);
+    return rc == ECAMD_EINVAL ? kDeclined : rc;
+}
+
+// Every other encode: the split into payloads, the codec over them, the CRC pass and headers.
+int encode_split(const EncodeJob& j)
+{
+    const Code& c = j.c;
+    int rc = launch_split(j, 0, j.stream);
     if (rc) return rc;
-    return finalize_ranges(dev, c, legacy, obj_size, frags, ss, fs, bs, nstripes, partial, q, stream);
+    if (c.backend == kBackendRs) {
+        rc = ecamd_rs_encode(c.k, c.m, j.payload0(), j.ss, j.fs, j.bs, j.nstripes, j.stream);
+    } else {
+        unsigned pb[32], db[32];
+        ecamd_xor_code_tables(c.k, c.m, c.hd, pb, db);
+        rc = xor_parity(j, pb, 0, j.stream);
+    }
+    return rc ? rc : finish(j, j.crc(), j.stream);
+}
+
+// ---- framed decode ----
+
+// The flat XOR decode-join's plan: one 0 / 1 matrix (coeff, outputs x inputs) over the surviving
+// fragments `inputs` (lost ones count as zero, as in xor_plan_apply) for the lost data fragments
+// `outputs`; every surviving data fragment is an input, for the copy.  No outputs: no plan (a lost
+// data fragment has no row), the caller decodes in place and joins.
+struct XorJoinPlan {
+    std::vector<int> inputs, outputs, coeff;
+};
+int xor_join_plan(const Code& c, const int* missing, XorJoinPlan* p)
+{
+    unsigned pb[32], db[32];
+    ecamd_xor_code_tables(c.k, c.m, c.hd, pb, db);
+    std::vector<int> outs(c.k + c.m);
+    std::vector<uint64_t> srcs(c.k + c.m);
+    int n = 0;
+    if (ecamd_xor_plan(1, c.k, c.m, c.hd, pb, db, missing, 0, outs.data(), srcs.data(), &n) < 0)
+        return dev_fail(ECAMD_EINVAL, "flat_xor_hd: erasure pattern not recoverable");
+    uint64_t lost = 0;
+    for (int i = 0; missing[i] >= 0; i++) lost |= uint64_t(1) << missing[i];
+    std::vector<int> douts;
+    std::vector<uint64_t> dsrc;
+    uint64_t need = 0, got = 0;
+    for (int i = 0; i < n; i++)
+        if (outs[i] < c.k) {
+            douts.push_back(outs[i]);
+            dsrc.push_back(srcs[i] & ~lost);
+            need |= srcs[i] & ~lost;
+            got |= uint64_t(1) << outs[i];
+        }
+    if (got != (lost & ((uint64_t(1) << c.k) - 1))) return 0;  // a lost data fragment without its row
+    for (int f = 0; f < c.k + c.m; f++)
+        if (!(lost >> f & 1) && (f < c.k || (need >> f & 1))) p->inputs.push_back(f);
+    for (uint64_t sm : dsrc)
+        for (int f : p->inputs) p->coeff.push_back(static_cast<int>(sm >> f & 1));
+    p->outputs = std::move(douts);
+    return 0;
+}
+
+// fragments_to_string: the streaming join kernel, or frame_join_kernel where 32-bit offsets do not
+// reach, the payloads are shorter than 32 bytes or knob frame_copy_stream is 0.
+int launch_join(int dev, int k, const JoinArgs& ja, void* stream)
+{
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const bool obj16 = aligned16(ja.obj) && ja.obj_stride % 16 == 0;
+    if (copy_fits32(k, ja.frag_stride, ja.bs, ja.size) && ja.bs >= 32 && g_tune.frame_copy_stream != 0) {
+        const CopyShape cs = copy_shape(ja.bs);
+        const int ja_knob = g_tune.frame_join_align;
+        const int align = (ja_knob == 1 || (ja_knob == 2 && ja.bs % 16)) && obj16 ? 1 : 0;
+        const int64_t span = static_cast<int64_t>(cs.threads) * cs.u;
+        const dim3 grid(copy_grid(dev, ja.bs / 16 + 2 + (align ? span - 1 : 0), k, ja.nstripes, cs)), block(cs.threads);
+        const bool dpp = g_tune.frame_copy_dpp != 0;
+        if (cs.u == 1)
+            hipLaunchKernelGGL((dpp ? frame_join_stream_kernel<1, true> : frame_join_stream_kernel<1, false>), grid,
+                               block, copy_lds(), st, ja, k, align);
+        else
+            hipLaunchKernelGGL((dpp ? frame_join_stream_kernel<4, true> : frame_join_stream_kernel<4, false>), grid,
+                               block, copy_lds(), st, ja, k, align);
+    } else
+        hipLaunchKernelGGL(frame_join_kernel, dim3(grid_for(dev, ((ja.size + 15) / 16) * ja.nstripes)), dim3(256), 0,
+                           st, ja);
+    HIP_TRY(hipGetLastError());
+    return 0;
 }
 
 }  // namespace
@@ -752,172 +1001,12 @@ int ecamd_frame_encode(int backend, int k, int m, int hd, int checksum, const vo
     if ((rc = check_frames(d_frags, stripe_stride, frag_stride, bs, k + m, nstripes))) return rc;
     if (nstripes == 0) return 0;
     if (!d_obj && obj_size) return dev_fail(ECAMD_EINVAL, "null object buffer");
-    auto* frags = static_cast<uint8_t*>(d_frags);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    uint8_t* p0 = frags + kHeaderBytes;
-    const bool aligned = aligned16(d_obj) && obj_stride % 16 == 0 && bs % 16 == 0;
-    if (backend == kBackendRs && aligned && static_cast<int64_t>(obj_size) == k * bs &&
-        g_tune.frame_unfused == 0) {
-        // The object fills the k payloads exactly (no padding): one launch reads it, copies the
-        // data into the payloads and writes the parity (10 MiB read + 14 MiB written per C3
-        // stripe instead of a separate split pass) -- with CRC32 checksums, the same launch also
-        // folds the payload checksums (no re-read of the 14 MiB).
-        if (checksum == kChksumCrc32) {
-            rc = encode_crc_fused(dev, c, legacy_crc(), d_obj, obj_stride, obj_size, frags, stripe_stride,
-                                  frag_stride, bs, nstripes, stream);
-            if (rc != ECAMD_EINVAL) return rc;
-            rc = encode_crc_cover(dev, c, legacy_crc(), d_obj, obj_stride, obj_size, frags, stripe_stride,
-                                  frag_stride, bs, nstripes, stream);
-            if (rc != ECAMD_EINVAL) return rc;
-        }
-        rc = rs_encode_copy(k, m, d_obj, obj_stride, p0, stripe_stride, frag_stride, bs, nstripes,
-                            stream);
-        if (rc) return rc;
-        return run_crc(dev, legacy_crc(), checksum == kChksumCrc32, frags, stripe_stride,
-                       frag_stride, kHeaderBytes, k + m, bs, nstripes, nullptr,
-                       header_args(c, checksum, bs, obj_size, 0), stream);
-    }
-    if (backend == kBackendRs && aligned16(d_obj) && obj_stride % 16 == 0 && g_tune.frame_unfused == 0 &&
-        g_tune.frame_copy_padded != 0) {
-        // Objects that do not fill the payloads exactly (any size: Swift's 1 MiB segments give
-        // bs = 104858): the same copy-through launch reads each chunk j*bs of the object with
-        // unaligned loads and reads zeros past the object's end, so no split pass either; with
-        // CRC32 checksums the whole tiles also fold them in the same launch (encode_crc_cover).
-        if (checksum == kChksumCrc32) {
-            rc = encode_crc_cover(dev, c, legacy_crc(), d_obj, obj_stride, obj_size, frags, stripe_stride,
-                                  frag_stride, bs, nstripes, stream);
-            if (rc != ECAMD_EINVAL) return rc;
-        }
-        // the whole 4 KiB tiles every payload holds on the copy-through launch; the rest by the
-        // copy-through codec of exactly [cover, bs) on the side stream beside it (knob
-        // frame_tail_fork), or after it by encode_tail (split + plain encode of the payloads' last tiles)
-        const int64_t last = static_cast<int64_t>(obj_size) - (k - 1) * bs;
-        const int64_t cover = last > 0 ? std::min(bs, last) / 4096 * 4096 : 0;
-        rc = ECAMD_EINVAL;
-        if (cover > 0 && fork_tail(bs - cover, checksum == kChksumCrc32)) {
-            // the rest [cover, bs) on the side stream, from the objects (exact range), beside the whole tiles
-            void* side = nullptr;
-            if ((rc = side_fork(dev, stream, &side))) return rc;
-            rc = rs_encode_copy(k, m, d_obj, obj_stride, p0, stripe_stride, frag_stride, bs, nstripes, side,
-                                static_cast<int64_t>(obj_size), cover);
-            const bool heads = checksum != kChksumCrc32;  // no checksum: the headers read no payload byte
-            if (rc == 0 && heads)
-                rc = run_crc(dev, legacy_crc(), false, frags, stripe_stride, frag_stride, kHeaderBytes, k + m, bs,
-                             nstripes, nullptr, header_args(c, checksum, bs, obj_size, 0), side);
-            if (rc == 0)
-                rc = rs_encode_copy(k, m, d_obj, obj_stride, p0, stripe_stride, frag_stride, bs, nstripes, stream,
-                                    static_cast<int64_t>(obj_size), 0, cover);
-            const int rj = side_join(dev, stream);
-            if (rc || rj || heads) return rc ? rc : rj;
-        } else if (cover > 0 && cover < bs && g_tune.frame_tail_bs != 0) {
-            if ((rc = rs_encode_copy(k, m, d_obj, obj_stride, p0, stripe_stride, frag_stride, bs, nstripes, stream,
-                                     static_cast<int64_t>(obj_size), 0, cover)))
-                return rc;
-            rc = encode_tail(dev, c, d_obj, obj_stride, obj_size, frags, stripe_stride, frag_stride, bs, nstripes,
-                             cover, stream);
-            if (rc == ECAMD_EINVAL)
-                rc = rs_encode_copy(k, m, d_obj, obj_stride, p0, stripe_stride, frag_stride, bs, nstripes, stream,
-                                    static_cast<int64_t>(obj_size), cover);
-        } else {
-            rc = rs_encode_copy(k, m, d_obj, obj_stride, p0, stripe_stride, frag_stride, bs, nstripes,
-                                stream, static_cast<int64_t>(obj_size));
-        }
-        if (rc) return rc;
-        return run_crc(dev, legacy_crc(), checksum == kChksumCrc32, frags, stripe_stride,
-                       frag_stride, kHeaderBytes, k + m, bs, nstripes, nullptr,
-                       header_args(c, checksum, bs, obj_size, 0), stream);
-    }
-    if (backend == kBackendXor && aligned16(d_obj) && obj_stride % 16 == 0 && g_tune.frame_unfused == 0 &&
-        g_tune.frame_xor_copy != 0 && g_tune.frame_copy_stream != 0 &&
-        copy_fits32(k, frag_stride, bs, static_cast<int64_t>(obj_size))) {
-        // flat XOR, copy-through (round 4): the whole 4 KiB tiles every object chunk holds in one
-        // launch that reads the chunks, writes the data payloads and the parity; the payloads' rest by
-        // the streaming split + the XOR of that range; then the CRC pass and headers.  Against split +
-        // XOR it moves 26 instead of 36 payload-sized units of HBM traffic per stripe at (10,6).
-        if (checksum == kChksumCrc32) {  // the checksums folded into the codec launch, as for RS
-            rc = encode_crc_cover(dev, c, legacy_crc(), d_obj, obj_stride, obj_size, frags, stripe_stride,
-                                  frag_stride, bs, nstripes, stream);
-            if (rc != ECAMD_EINVAL) return rc;
-        }
-        const int64_t last = static_cast<int64_t>(obj_size) - (k - 1) * bs;
-        const int64_t cover = last > 0 ? std::min(bs, last) / 4096 * 4096 : 0;
-        unsigned pb[32], db[32];
-        ecamd_xor_code_tables(k, m, hd, pb, db);
-        // the payloads' rest [cover, bs): split, then the XOR of that range (bytes disjoint from the
-        // copy-through launch: on the side stream beside it, knob frame_tail_fork)
-        auto rest = [&](void* st2) {
-            int r = split_range(dev, k, d_obj, obj_stride, obj_size, frags, stripe_stride, frag_stride, bs, nstripes,
-                                cover, st2);
-            if (r == 0) {
-                std::vector<int64_t> in_off(k), out_off(m);
-                for (int j = 0; j < k; j++) in_off[j] = j * frag_stride;
-                for (int o = 0; o < m; o++) out_off[o] = (k + o) * frag_stride;
-                r = ecamd_xor_apply_strided(pb, m, k, p0 + cover, stripe_stride, in_off.data(), p0 + cover,
-                                            stripe_stride, out_off.data(), bs - cover, nstripes, st2);
-            }
-            return r == ECAMD_EINVAL ? dev_fail(ECAMD_EHIP, "framed xor encode: tail failed") : r;
-        };
-        if (cover > 0 && fork_tail(bs - cover, checksum == kChksumCrc32)) {
-            void* side = nullptr;
-            if ((rc = side_fork(dev, stream, &side))) return rc;
-            rc = rest(side);
-            const bool heads = checksum != kChksumCrc32;  // no checksum: the headers read no payload byte
-            if (rc == 0 && heads)
-                rc = run_crc(dev, legacy_crc(), false, frags, stripe_stride, frag_stride, kHeaderBytes, k + m, bs,
-                             nstripes, nullptr, header_args(c, checksum, bs, obj_size, 0), side);
-            if (rc == 0)  // ECAMD_EINVAL (declined): the split path below rewrites everything after the join
-                rc = xor_encode_copy(pb, k, m, d_obj, obj_stride, p0, stripe_stride, frag_stride, bs, cover, nstripes,
-                                     stream);
-            const int rj = side_join(dev, stream);
-            if (rj) return rj;
-            if (rc == 0 && heads) return 0;
-        } else {
-            rc = cover > 0 ? xor_encode_copy(pb, k, m, d_obj, obj_stride, p0, stripe_stride, frag_stride, bs, cover,
-                                             nstripes, stream)
-                           : ECAMD_EINVAL;
-            // from here on a failure is an error: part of the payloads is written
-            if (rc == 0 && cover < bs && (rc = rest(stream))) return rc;
-        }
-        if (rc == 0)
-            return run_crc(dev, legacy_crc(), checksum == kChksumCrc32, frags, stripe_stride, frag_stride,
-                           kHeaderBytes, k + m, bs, nstripes, nullptr, header_args(c, checksum, bs, obj_size, 0),
-                           stream);
-        if (rc != ECAMD_EINVAL) return rc;
-    }
-    SplitArgs sa{static_cast<const uint8_t*>(d_obj), obj_stride, static_cast<int64_t>(obj_size),
-                 frags, stripe_stride, frag_stride, bs, k, nstripes, aligned ? 1 : 0};
-    if (copy_fits32(k, frag_stride, bs, static_cast<int64_t>(obj_size)) && g_tune.frame_copy_stream != 0) {
-        const CopyShape cs = copy_shape(bs);
-        const dim3 grid(copy_grid(dev, (bs + 15) / 16, k, nstripes, cs)), block(cs.threads);
-        const bool dpp = g_tune.frame_copy_dpp != 0;
-        if (cs.u == 1)
-            hipLaunchKernelGGL((dpp ? frame_split_stream_kernel<1, true> : frame_split_stream_kernel<1, false>), grid,
-                               block, copy_lds(), st, sa);
-        else
-            hipLaunchKernelGGL((dpp ? frame_split_stream_kernel<4, true> : frame_split_stream_kernel<4, false>), grid,
-                               block, copy_lds(), st, sa);
-    } else
-        hipLaunchKernelGGL(frame_split_kernel, dim3(grid_for(dev, ((bs + 15) / 16) * k * nstripes)),
-                           dim3(256), 0, st, sa);
-    HIP_TRY(hipGetLastError());
-    if (backend == kBackendRs) {
-        rc = ecamd_rs_encode(k, m, p0, stripe_stride, frag_stride, bs, nstripes, stream);
-    } else {
-        // xor_code_encode accumulates into zeroed parity (src/builtin/xor_codes/xor_code.c:180-191):
-        // parity j = XOR of the data fragments in parity_bms[j].
-        unsigned pb[32], db[32];
-        ecamd_xor_code_tables(k, m, hd, pb, db);
-        std::vector<int64_t> in_off(k), out_off(m);
-        for (int j = 0; j < k; j++) in_off[j] = j * frag_stride;
-        for (int r = 0; r < m; r++) out_off[r] = (k + r) * frag_stride;
-        rc = ecamd_xor_apply_strided(pb, m, k, p0, stripe_stride, in_off.data(), p0, stripe_stride,
-                                     out_off.data(), bs, nstripes, stream);
-    }
-    if (rc) return rc;
-    const bool legacy = legacy_crc();
-    return run_crc(dev, legacy, checksum == kChksumCrc32, frags, stripe_stride, frag_stride,
-                   kHeaderBytes, k + m, bs, nstripes, nullptr, header_args(c, checksum, bs, obj_size, 0),
-                   stream);
+    const EncodeJob job{dev, c, legacy_crc(), checksum, d_obj, obj_stride, obj_size, static_cast<uint8_t*>(d_frags),
+                        stripe_stride, frag_stride, bs, nstripes, stream};
+    rc = encode_rs_exact(job);
+    if (rc == kDeclined) rc = encode_rs_padded(job);
+    if (rc == kDeclined) rc = encode_xor_copy(job);
+    return rc == kDeclined ? encode_split(job) : rc;
 }
 
 int ecamd_frame_decode(int backend, int k, int m, int hd, const int* missing, void* d_frags,
@@ -957,33 +1046,11 @@ int ecamd_frame_decode(int backend, int k, int m, int hd, const int* missing, vo
         // flat XOR, as the RS decode-join: the plan is one 0 / 1 matrix over the surviving fragments
         // (lost ones count as zero, as in xor_plan_apply), so the lost data go straight into the
         // objects and the surviving data payloads are copied there by the same launch
-        unsigned pb[32], db[32];
-        ecamd_xor_code_tables(k, m, hd, pb, db);
-        std::vector<int> outs(k + m);
-        std::vector<uint64_t> srcs(k + m);
-        int n = 0;
-        if (ecamd_xor_plan(1, k, m, hd, pb, db, missing, 0, outs.data(), srcs.data(), &n) < 0)
-            return dev_fail(ECAMD_EINVAL, "flat_xor_hd: erasure pattern not recoverable");
-        uint64_t lost = 0;
-        for (int i = 0; missing[i] >= 0; i++) lost |= uint64_t(1) << missing[i];
-        std::vector<int> douts, inputs, coeff;
-        std::vector<uint64_t> dsrc;
-        uint64_t need = 0, got = 0;
-        for (int i = 0; i < n; i++)
-            if (outs[i] < k) {
-                douts.push_back(outs[i]);
-                dsrc.push_back(srcs[i] & ~lost);
-                need |= srcs[i] & ~lost;
-                got |= uint64_t(1) << outs[i];
-            }
-        if (got == (lost & ((uint64_t(1) << k) - 1))) {  // every lost data fragment has its row
-            for (int f = 0; f < k + m; f++)
-                if (!(lost >> f & 1) && (f < k || (need >> f & 1))) inputs.push_back(f);
-            for (uint64_t sm : dsrc)
-                for (int f : inputs) coeff.push_back(static_cast<int>(sm >> f & 1));
-            return xor_decode_join(k, inputs, douts, coeff, p0, stripe_stride, frag_stride, d_obj, obj_stride, bs,
-                                   nstripes, stream, static_cast<int64_t>(obj_size));
-        }
+        XorJoinPlan plan;
+        if ((rc = xor_join_plan(c, missing, &plan))) return rc;
+        if (!plan.outputs.empty())
+            return xor_decode_join(k, plan.inputs, plan.outputs, plan.coeff, p0, stripe_stride, frag_stride, d_obj,
+                                   obj_stride, bs, nstripes, stream, static_cast<int64_t>(obj_size));
     }
     if (data_missing) {  // the systematic fast path (src/erasurecode.c:597-607) skips this
         if (backend == kBackendRs)
@@ -997,26 +1064,7 @@ int ecamd_frame_decode(int backend, int k, int m, int hd, const int* missing, vo
     JoinArgs ja{frags, stripe_stride, frag_stride, bs, static_cast<uint8_t*>(d_obj), obj_stride,
                 static_cast<int64_t>(obj_size), nstripes,
                 (aligned16(d_obj) && obj_stride % 16 == 0 && bs % 16 == 0) ? 1 : 0};
-    if (copy_fits32(k, frag_stride, bs, static_cast<int64_t>(obj_size)) && bs >= 32 &&
-        g_tune.frame_copy_stream != 0) {
-        const CopyShape cs = copy_shape(bs);
-        const int ja_knob = g_tune.frame_join_align;
-        const int align = (ja_knob == 1 || (ja_knob == 2 && bs % 16)) && aligned16(d_obj) && obj_stride % 16 == 0 ? 1 : 0;
-        const int64_t span = static_cast<int64_t>(cs.threads) * cs.u;
-        const dim3 grid(copy_grid(dev, bs / 16 + 2 + (align ? span - 1 : 0), k, nstripes, cs)), block(cs.threads);
-        const bool dpp = g_tune.frame_copy_dpp != 0;
-        if (cs.u == 1)
-            hipLaunchKernelGGL((dpp ? frame_join_stream_kernel<1, true> : frame_join_stream_kernel<1, false>), grid,
-                               block, copy_lds(), static_cast<hipStream_t>(stream), ja, k, align);
-        else
-            hipLaunchKernelGGL((dpp ? frame_join_stream_kernel<4, true> : frame_join_stream_kernel<4, false>), grid,
-                               block, copy_lds(), static_cast<hipStream_t>(stream), ja, k, align);
-    } else
-        hipLaunchKernelGGL(frame_join_kernel,
-                           dim3(grid_for(dev, ((static_cast<int64_t>(obj_size) + 15) / 16) * nstripes)),
-                           dim3(256), 0, static_cast<hipStream_t>(stream), ja);
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return launch_join(dev, k, ja, stream);
 }
 
 int ecamd_frame_reconstruct(int backend, int k, int m, int hd, int checksum, const int* missing,
@@ -1124,11 +1172,9 @@ int ecamd_xor_encode(int k, int m, int hd, void* base, int64_t stripe_stride, in
     // is written here (overwriting whatever the parity slots held)
     unsigned pb[32], db[32];
     ecamd_xor_code_tables(k, m, hd, pb, db);
-    std::vector<int64_t> in_off(k), out_off(m);
-    for (int j = 0; j < k; j++) in_off[j] = j * frag_stride;
-    for (int r = 0; r < m; r++) out_off[r] = (k + r) * frag_stride;
-    return ecamd_xor_apply_strided(pb, m, k, base, stripe_stride, in_off.data(), base, stripe_stride,
-                                   out_off.data(), blocksize, nstripes, stream);
+    const ParityOffsets off(k, m, frag_stride);
+    return ecamd_xor_apply_strided(pb, m, k, base, stripe_stride, off.in.data(), base, stripe_stride,
+                                   off.out.data(), blocksize, nstripes, stream);
 }
 
 int ecamd_xor_decode(int k, int m, int hd, const int* missing, int decode_parity, void* base,

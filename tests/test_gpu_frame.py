@@ -899,6 +899,58 @@ def test_frame_xor_copy_through_matches_split(F, k, m, hd, ct):
         assert all(out[0][S - 1, i].tobytes() == want[i] for i in range(k + m)), size
 
 
+_NONE, _CRC = ec_api.CHKSUM_NONE, ec_api.CHKSUM_CRC32
+# (code, object bytes per data fragment, checksum, knobs): branches of the framed encode's strategies
+# ("Framed encode / decode / reconstruct / verify", the branch table) that no test above
+# reaches, at the smallest payloads that take them -- one 4 KiB tile, or one tile and a 1 KiB rest
+# whose last chunk is 6 bytes short
+ENCODE_BRANCHES = [
+    # RS, object fills the payloads, no checksum, payloads that are not whole 16 KiB tiles
+    ("rs", 4, 2, 0, 4096, 0, _NONE, {}),
+    # RS padded, rest after the whole tiles: encode_tail declines (no streaming split), the LDS-table launch
+    ("rs", 4, 2, 0, 4096 + 1024, 6, _NONE, {"frame_copy_stream": 0, "frame_tail_fork": 0}),
+    # RS padded with CRC32 and no crc variant: the forked rest, then the CRC pass after the join
+    ("rs", 4, 2, 0, 4096 + 1024, 6, _CRC, {"frame_crc_cover": 0, "frame_tail_fork": 2}),
+    # the crc variant declines after its forked rest ran (no bitsliced kernel); the strategy forks again
+    ("rs", 10, 4, 0, 4096 + 1024, 6, _CRC, {"bitslice": 0, "frame_tail_fork": 2}),
+    ("xor", 3, 3, 3, 4096 + 1024, 6, _CRC, {"bitslice": 0, "frame_tail_fork": 2}),
+    # flat XOR with CRC32 and no streaming split: the first-version split kernel, XOR, CRC pass
+    ("xor", 3, 3, 3, 4096 + 1024, 6, _CRC, {"frame_copy_stream": 0}),
+]
+
+
+@pytest.mark.parametrize("name,k,m,hd,per,short,ct,knobs", ENCODE_BRANCHES,
+                         ids=[f"{c[0]}_{c[1]}_{c[2]}_{c[4]}_{c[6]}_" + "_".join(f"{n}{v}" for n, v in c[7].items())
+                              for c in ENCODE_BRANCHES])
+def test_frame_encode_branches_match_split(F, name, k, m, hd, per, short, ct, knobs):
+    """One framed encode per branch of ecamd_frame_encode's strategies that the tests above leave out:
+    fragments equal the split-then-encode path's (knob frame_unfused 1) and the restated framing."""
+    from liberasurecode_amd import _lib
+    be = _backend(name)
+    S = 3
+    size = k * per - short
+    objs = _objects(S, size, k * 37 + m + size)
+    d = _lib.dev()
+    out = []
+    try:
+        # the split path under the default knobs first, then the branch under its own
+        for unfused, tune in ((1, {"bitslice": 2}), (0, {"bitslice": 2, **knobs})):
+            _lib.check(d.ecamd_tune(b"frame_unfused", unfused), "tune")
+            for knob, v in tune.items():
+                _lib.check(d.ecamd_tune(knob.encode(), v), "tune")
+            fb = F.FrameBatch(be, k, m, size, S, hd=hd or 3, checksum=ct)
+            fb.encode(_upload_objects(objs, fb.obj_stride))
+            out.append(fb.fragments())
+    finally:
+        for knob, default in (("frame_unfused", 0), ("bitslice", 1), ("frame_copy_stream", 1), ("frame_tail_fork", -1),
+                              ("frame_crc_cover", 1)):
+            d.ecamd_tune(knob.encode(), default)
+    assert np.array_equal(out[0], out[1])
+    for s in range(S):
+        want = expected_stripe(be, k, m, hd, objs[s], ct)
+        assert all(out[1][s, i].tobytes() == want[i] for i in range(k + m)), s
+
+
 @pytest.mark.parametrize("k,m,hd,missing", [(10, 6, 4, [0, 1, 2]), (10, 6, 4, [3, 11, 14]), (3, 3, 3, [1, 4]),
                                             (10, 5, 3, [9, 12]), (20, 6, 4, [19, 0, 7]), (12, 6, 4, [5])])
 def test_frame_xor_decode_join_matches(F, k, m, hd, missing):
