@@ -533,6 +533,50 @@ int ecamd_xor_decode_multi(int k, int m, int hd, const int *missing, int missing
  * which kernel ran: passes of at most "small_chunks" chunks take xor_small_kernel and do not count). */
 long long ecamd_xor_stream_launches(void);
 
+/* ---- flat_xor_hd decode from device masks: ecamd_rs_decode_masks' counterpart for the flat XOR codes ----
+ * d_lost (nstripes uint32, DEVICE memory) holds one mask per stripe, bit f set when fragment f of stripe s
+ * is lost; the word is read on the device, in stream order, exactly as ecamd_rs_decode_masks reads it.
+ * Per stripe, with L = d_lost[s]:
+ *   L == 0                          nothing of the stripe is read or written; d_result[s] = 0.
+ *   a bit >= k+m, or hd or more     not recoverable -- the reference refuses every list of hd or more
+ *   bits                            fragments (get_failure_pattern: GE_HD), whatever the code could solve:
+ *                                   nothing of the stripe is written; d_result[s] = 0x80000000 | popcount(L).
+ *   otherwise                       the outputs are the lost data fragments, ascending, then -- with
+ *                                   decode_parity -- the lost parity fragments, ascending.  Each is the XOR
+ *                                   of the surviving fragments that ecamd_xor_plan(op 1, the ascending list
+ *                                   of L, decode_parity 1) names for it, the bits of lost fragments dropped:
+ *                                   the bytes xor_hd_decode leaves when the lost slots were ZERO-FILLED,
+ *                                   which is how the frontend calls it and what ecamd_xor_decode_multi
+ *                                   documents.  d_result[s] = the number of fragments written (0 when only
+ *                                   parity is lost and decode_parity is 0).
+ * Lost slots are never read: they may hold anything.  Never written: surviving fragments, lost parity
+ * without decode_parity, every slot of an unrecoverable stripe, the bytes between blocksize and frag_stride.
+ * d_result (nstripes uint32, device memory, may be NULL).  d_counts (3 uint32, device memory, may be NULL)
+ * is overwritten with the number of stripes left alone (result 0), rebuilt, and unrecoverable.
+ * Any blocksize >= 1, odd ones included: XOR has no 16-bit word.
+ * There is no host dependence inside the call: no stream synchronise, no copy to the host, no launch whose
+ * shape depends on the masks, no map-cache entry, no xor_stream_kernel launch and no compile.  A code has
+ * at most 2952 recoverable patterns ((20,6,4): the masks of fewer than hd bits), so its whole decode is one
+ * table of 16-byte entries (ecamd_xor_decode_masks_plan, ecamd_host.h) indexed by the rank of the mask, and
+ * nothing is solved on the device.  The launches are fixed: the data kernel (per stripe: the mask's rank and
+ * entry as scalars, 128-bit loads of the union of the entry's sources -- each fragment once, however many
+ * outputs it feeds --, 128-bit stores of the outputs; a stripe with nothing to write costs one word load
+ * per workgroup that visits it; tiles of 4096 bytes, the last partial 16-byte chunk byte-exact; no LDS;
+ * its first tile column writes d_result), and with d_counts a one-workgroup count.  The first call for a
+ * (k, m, hd) on a device uploads that code's table, once; there is no per-stream scratch.
+ * ECAMD_EINVAL, with the data and the arrays untouched, for a code init_xor_hd_code rejects, a null d_lost
+ * or base, the layout errors of the other strided calls (16-byte aligned base and strides, frag_stride >=
+ * blocksize >= 1) and nstripes < 0.  nstripes == 0 returns 0 and writes nothing.
+ * Knob "pairs_grid" > 0 caps both grid dimensions of the data kernel as it does for decode_masks_kernel.
+ * When to prefer ecamd_xor_decode_multi: DESIGN.md "Decode from device masks", INTEGRATION.md. */
+int ecamd_xor_decode_masks(int k, int m, int hd, const uint32_t *d_lost, int decode_parity, void *base,
+                           int64_t stripe_stride, int64_t frag_stride, int64_t blocksize, int nstripes,
+                           uint32_t *d_result /* may be NULL */, uint32_t *d_counts /* 3 words, may be NULL */,
+                           void *stream);
+/* Launches of xor_decode_masks_kernel (the data kernel) enqueued by this process: one per call with a
+ * non-empty batch. */
+long long ecamd_xor_decode_masks_launches(void);
+
 /* ---- synchronous host-buffer execution (used by the per-call drop-in ABIs) ----
  * Pooled pinned staging + two streams, chunked so host copies overlap PCIe and the kernel.
  * Calls are spread round-robin over the visible devices (or ECAMD_PERCALL_DEVICES, see
@@ -615,10 +659,12 @@ int ecamd_frame_reconstruct(int backend, int k, int m, int hd, int checksum, con
 int ecamd_frame_verify(int nfrag, int64_t blocksize, int legacy, const void *d_frags,
                        int64_t stripe_stride, int64_t frag_stride, int nstripes, uint32_t *d_status,
                        uint32_t *d_crc, void *stream);
-/* The glue from the audit to ecamd_rs_decode_masks: d_masks[s] (nstripes uint32, device memory) gets
- * bit f when d_frag_status[s*nfrag + f] & bits is non-zero; d_frag_status has the layout
- * ecamd_frame_verify writes, nfrag <= 32.  One small kernel, asynchronous on `stream`.  With it
+/* The glue from the audit to ecamd_rs_decode_masks (backend 6) and ecamd_xor_decode_masks (backend 3):
+ * d_masks[s] (nstripes uint32, device memory) gets bit f when d_frag_status[s*nfrag + f] & bits is
+ * non-zero; d_frag_status has the layout ecamd_frame_verify writes, nfrag <= 32.  One small kernel,
+ * asynchronous on `stream`.  With it
  *   ecamd_frame_verify -> ecamd_frame_status_masks(bits = 1 << 4) -> ecamd_rs_decode_masks(base = d_frags + 80)
+ *                                                                 or ecamd_xor_decode_masks(base = d_frags + 80)
  * heals payload damage of framed stripes on one stream with one wait at the end: the header still
  * holds the original payload's CRC32, so the rebuilt payload matches it again.  Fragments with a bad
  * HEADER (bits 0-3) are not covered: the decode rebuilds payloads only and no header is restamped, so

@@ -161,6 +161,18 @@ int ecamd_xor_plan(int op, int k, int m, int hd, const unsigned int *parity_bms,
                    const unsigned int *data_bms, const int *missing, int arg, int *outputs,
                    uint64_t *sources, int *nout);
 
+/* The decode table of a supported (k, m, hd) code, as ecamd_xor_decode_masks (ecamd.h) uploads it: one
+ * 16-byte entry per ascending list of fewer than hd lost fragments, the empty list included, at the rank
+ * of the list's mask (csrc/hip/ecamd_xor_masks_plan.hpp: xor_masks_rank, and the entry's layout --
+ * byte 0 the number of outputs, bytes 1-3 the output fragments, three uint32 source masks).  Entry by
+ * entry it is ecamd_xor_plan(op 1, the list, decode_parity 1) with the outputs ascending and the bits of
+ * the lost fragments dropped from every source: the bytes xor_hd_decode leaves when the lost slots were
+ * zero-filled.  The outputs below k, unchanged, are the plan of decode_parity 0.
+ * Returns the number of entries, sum of C(k+m, t) over t < hd (at most 2952, at (20,6,4)); the table is
+ * written when it is not NULL and `capacity` (in entries) is at least that number.  -1 for a code
+ * init_xor_hd_code rejects; -2, which no shipped code returns, if a plan does not have that form. */
+int ecamd_xor_decode_masks_plan(int k, int m, int hd, void *table, int capacity);
+
 /* xor_hd_fragments_needed (xor_hd_code.c:209-412); needed ends with -1. */
 int ecamd_xor_fragments_needed(int k, int m, int hd, const unsigned int *parity_bms,
                                const unsigned int *data_bms, const int *to_reconstruct,

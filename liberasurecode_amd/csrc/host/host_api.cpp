@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "bitslice.hpp"
+#include "ecamd_xor_masks_plan.hpp"
 #include "gf16.hpp"
 #include "tables.hpp"
 #include "xor_plan.hpp"
@@ -263,6 +264,45 @@ int ecamd_xor_plan(int op, int k, int m, int hd, const unsigned int* parity_bms,
     }
     *nout = static_cast<int>(p.outputs.size());
     return p.rc;
+}
+
+int ecamd_xor_decode_masks_plan(int k, int m, int hd, void* table, int capacity)
+{
+    XorCode c;
+    if (k <= 0 || m <= 0 || !xor_code_lookup(k, m, hd, c)) return -1;
+    const int n = k + m;
+    if (n > 32 || hd - 1 > kXorMasksMaxOut) return -2;
+    const int count = xor_masks_count(n, hd);
+    if (!table || capacity < count) return count;
+    auto* tab = static_cast<XorMasksEntry*>(table);
+    std::memset(tab, 0, sizeof(XorMasksEntry) * static_cast<size_t>(count));
+    for (int t = 0; t < hd; t++) {  // every ascending list of t fragments, in lexicographic order
+        std::vector<int> lost(static_cast<size_t>(t));
+        for (int i = 0; i < t; i++) lost[i] = i;
+        for (;;) {
+            uint32_t L = 0;
+            for (int f : lost) L |= 1u << f;
+            const XorPlan p = xor_plan_decode(c, lost, 1);
+            const int32_t rank = xor_masks_rank(n, hd, L);
+            if (p.rc != 0 || p.outputs.size() != lost.size() || rank < 0 || rank >= count) return -2;
+            XorMasksEntry& e = tab[rank];
+            for (int r = 0; r < t; r++) {  // the outputs ascending, whatever the plan's order
+                const auto at = std::find(p.outputs.begin(), p.outputs.end(), lost[r]);
+                if (at == p.outputs.end()) return -2;
+                const uint64_t src = p.sources[static_cast<size_t>(at - p.outputs.begin())] & ~static_cast<uint64_t>(L);
+                if (src == 0 || (src >> n) != 0) return -2;
+                e.out[r] = static_cast<uint8_t>(lost[r]);
+                e.src[r] = static_cast<uint32_t>(src);
+            }
+            e.n_out = static_cast<uint8_t>(t);
+            int i = t - 1;
+            while (i >= 0 && lost[i] == n - t + i) i--;
+            if (i < 0) break;
+            lost[i]++;
+            for (int j = i + 1; j < t; j++) lost[j] = lost[j - 1] + 1;
+        }
+    }
+    return count;
 }
 
 int ecamd_xor_fragments_needed(int k, int m, int hd, const unsigned int* parity_bms,

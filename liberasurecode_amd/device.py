@@ -334,13 +334,8 @@ def xor_correct(k, m, hd, lay: Layout, stream=None, missing=()):
         _s(stream)), lay, stream, "xor_correct", False)
 
 
-def rs_decode_masks(k, m, lost_masks, lay: Layout, rebuild_parity=True, stream=None):
-    """ecamd_rs_decode_masks: rebuild in place the fragments each stripe lost, lost_masks[s] the mask of
-    stripe s (bit f: fragment f is lost).  The masks are uploaded to device memory, where the call reads
-    them; there is no host wait inside the call.  Returns (result, counts) after this function's own
-    synchronise: result[s] = fragments rebuilt, 0 for an empty mask, 0x80000000 | popcount for a mask that
-    cannot be recovered (that stripe is not written); counts = (left alone, rebuilt, unrecoverable).
-    blocksize must be even, m <= 8."""
+def _decode_masks(call, lost_masks, lay, stream, what):
+    """call(d_lost, d_result, d_counts) on an upload of lost_masks, then a synchronise: (result, counts)."""
     n = max(lay.nstripes, 1)
     masks = np.ascontiguousarray(np.asarray(lost_masks, dtype=np.uint32).reshape(-1))
     if masks.size != lay.nstripes:
@@ -350,9 +345,7 @@ def rs_decode_masks(k, m, lost_masks, lay: Layout, rebuild_parity=True, stream=N
         check(dev().ecamd_memset(buf.ptr, 0, 8 * n + 16), "memset")
         if lay.nstripes:
             buf.upload(masks)
-        check(dev().ecamd_rs_decode_masks(k, m, buf.ptr, int(rebuild_parity), lay.buf.ptr, lay.stripe_stride,
-                                          lay.frag_stride, lay.blocksize, lay.nstripes, buf.ptr + 4 * n,
-                                          buf.ptr + 8 * n, _s(stream)), "rs_decode_masks")
+        check(call(buf.ptr, buf.ptr + 4 * n, buf.ptr + 8 * n), what)
         if stream is not None:
             stream.synchronize()
         else:
@@ -363,10 +356,33 @@ def rs_decode_masks(k, m, lost_masks, lay: Layout, rebuild_parity=True, stream=N
         buf.free()
 
 
+def rs_decode_masks(k, m, lost_masks, lay: Layout, rebuild_parity=True, stream=None):
+    """ecamd_rs_decode_masks: rebuild in place the fragments each stripe lost, lost_masks[s] the mask of
+    stripe s (bit f: fragment f is lost).  The masks are uploaded to device memory, where the call reads
+    them; there is no host wait inside the call.  Returns (result, counts) after this function's own
+    synchronise: result[s] = fragments rebuilt, 0 for an empty mask, 0x80000000 | popcount for a mask that
+    cannot be recovered (that stripe is not written); counts = (left alone, rebuilt, unrecoverable).
+    blocksize must be even, m <= 8."""
+    return _decode_masks(lambda lost, res, cnt: dev().ecamd_rs_decode_masks(
+        k, m, lost, int(rebuild_parity), lay.buf.ptr, lay.stripe_stride, lay.frag_stride, lay.blocksize, lay.nstripes,
+        res, cnt, _s(stream)), lost_masks, lay, stream, "rs_decode_masks")
+
+
+def xor_decode_masks(k, m, hd, lost_masks, lay: Layout, decode_parity=True, stream=None):
+    """ecamd_xor_decode_masks: the same for a flat_xor_hd code.  A mask of hd or more fragments cannot be
+    recovered (the reference refuses it); a rebuilt fragment holds what xor_hd_decode leaves when the lost
+    slots were zero-filled, as after xor_decode_multi; any blocksize >= 1.  Returns (result, counts) as
+    rs_decode_masks."""
+    return _decode_masks(lambda lost, res, cnt: dev().ecamd_xor_decode_masks(
+        k, m, hd, lost, int(decode_parity), lay.buf.ptr, lay.stripe_stride, lay.frag_stride, lay.blocksize, lay.nstripes,
+        res, cnt, _s(stream)), lost_masks, lay, stream, "xor_decode_masks")
+
+
 def frame_status_masks(nfrag, d_frag_status, bits, nstripes, d_masks, stream=None):
     """ecamd_frame_status_masks: d_masks[s] (device address) gets bit f when word s*nfrag + f of
     d_frag_status (device address, as ecamd_frame_verify writes it) has any of `bits`.  Asynchronous on
-    `stream`: the masks are meant for ecamd_rs_decode_masks on the same stream."""
+    `stream`: the masks are meant for ecamd_rs_decode_masks (rs_vand) or ecamd_xor_decode_masks
+    (flat_xor_hd) on the same stream."""
     check(dev().ecamd_frame_status_masks(nfrag, d_frag_status, bits, nstripes, d_masks, _s(stream)),
           "frame_status_masks")
 
