@@ -1,49 +1,47 @@
-// ecamd_check.hip -- stripe consistency check, locate and scrub (ecamd_rs_check / ecamd_xor_check,
-// ecamd_rs_locate / ecamd_xor_locate, ecamd_rs_scrub / ecamd_xor_scrub; DESIGN.md "Consistency check",
-// "Locate and scrub").
+// ecamd_check.hip -- stripe integrity on the device: check, locate, the pair stage, correct, scrub, and the
+// same for flat XOR stripes with fragments missing (DESIGN.md "Consistency check", "Locate and scrub",
+// "Two bad fragments", "Correct on the device", "Degraded flat XOR stripes", "Check driver: one call record").
 //
-// d_status[s]: the checked fragments of stripe s that disagree with its inputs.  d_suspects[s]
-// (locate): the fragments that ALONE explain every disagreement of stripe s.
+// d_status[s]: the checked fragments of stripe s that disagree with its inputs.  d_suspects[s] (locate):
+// the fragments that ALONE explain every disagreement of stripe s.  d_pairs[s] (pair stage): the two
+// fragments that together do.  A correcting call then XORs the error values into the stored words.
 //
-// Fused stage (rs_vand, whole bitsliced tiles; ecamd::check_fused in ecamd_device.hip): the check
-// form of the bitsliced kernel over the syndrome map [A | I] reads the K inputs and the R checked
-// fragments and writes only the status bits of inconsistent stripes; its locate form also ANDs the
-// candidates it rules out away from the suspects.  Fused stage (flat XOR, whole 4 KiB or 1 KiB tiles;
-// xor_check_kernel below): the syndromes straight from 128-bit loads of all k + m fragments, the same
-// two forms.  Generic stage (everything else: tails, small fragments, shapes the fused kernels
-// decline, maps still compiling, knob bitslice 0, knob xor_check_fused 0):
-// the strided applies compute the expected fragments into the stream context's scratch (slot
-// kCheckScratchSlot, at most kCheckScratchBytes, so long batches go stripe chunk by stripe chunk and
-// long fragments byte range by byte range) and check_compare_kernel / locate_compare_kernel compare
-// them with the stored ones.  Both stages OR into the same status words and AND into the same
-// suspects, which run_check sets first; locate_finalize_kernel masks the suspects with the
-// participating fragments and clears them on clean stripes -- all on the caller's stream, in order.
+// The driver.  Every entry point builds one CheckCall -- where the stripes lie (StripeLayout), the stream,
+// the result arrays, how far the call goes -- and hands it to its family's builder (rs_call, xor_call,
+// xor_degraded_call) through check_entry: device, the family's test of the code, check_layout, the
+// CheckPlan, the caller's `checked` / `covered` word, run_check.  run_check lays the plan's fragments out
+// as Participants (the K inputs, then the R checked rows) once, and every stage reads that record:
+//   fused stage    whole tiles, by the plan's Fused tag.  rs_vand: ecamd::check_fused (ecamd_device.hip), the
+//                  check / locate form of the bitsliced kernel over the syndrome map [A | I].  Flat XOR:
+//                  xor_check_kernel below, the syndromes straight from 128-bit loads of every fragment, or
+//                  (fragments missing) of the participants alone (XorCheckSlotArgs).
+//   generic stage  everything else -- tails, small fragments, shapes the fused kernels decline, maps still
+//                  compiling, knob bitslice 0, knob xor_check_fused 0: the strided applies compute the
+//                  expected fragments into the stream context's scratch (slot kCheckScratchSlot, at most
+//                  kCheckScratchBytes, so long batches go stripe chunk by stripe chunk and long fragments
+//                  byte range by byte range) and check_compare_kernel / locate_compare_kernel compare.
+//   finalize       (locate) locate_finalize_kernel masks the suspects with the participating fragments
+//                  and clears them on clean stripes.  Both stages before it OR into the same status
+//                  words and AND into the same suspects, which run_check sets first.
+//   pair stage     (rs_vand, R >= 4) locate_pairs_kernel reads the dirty stripes without a suspect again
+//                  and ORs into d_pairs[s] the fragments its words need; pairs_finalize_kernel keeps a
+//                  word of exactly two bits.
+//   correct stage  correct_kernel reads the three words of each stripe and XORs the error values of a
+//                  located fragment or pair into the stored words.
+// All of it on the caller's stream, in order, with no host wait; only the scrubs wait, in scrub_located.
 //
-// Pair stage (ecamd_rs_locate_pairs, ecamd_rs_scrub_pairs; rs_vand with R >= 4 checked fragments):
-// after the finalize, locate_pairs_kernel reads the dirty stripes that have no suspect again and ORs
-// into d_pairs[s] the fragments its words need; pairs_finalize_kernel keeps a word of exactly two
-// bits (DESIGN.md "Two bad fragments").
-//
-// Correct stage (ecamd_rs_correct, ecamd_xor_correct): after the locate or the pair stage,
-// correct_kernel reads the three words of each stripe and XORs the error values of a located fragment
-// or pair into the stored words -- on the same stream, with no host wait (DESIGN.md "Correct on the
-// device").  The device tables of the pair and correct stages are laid out and built here, beside the
-// kernels that read them (PairsTable / check_map_pairs, CorrectTable / check_map_correct /
-// xor_correct_table); the cached check map of ecamd_rs.hip only owns the memory of its two (OnceTable).
-// stripe_grid, the grid of the stripe-by-stripe kernels, is shared with ecamd_decode_masks.hip.
-//
-// Flat XOR with fragments missing (ecamd_xor_check_degraded, ecamd_xor_locate_degraded,
-// ecamd_xor_correct_degraded): the rows of ecamd_xor_check_plan_degraded through the same stages -- the
-// fused kernel over the participants alone (XorCheckSlotArgs), the generic stage and correct_kernel over
-// a CheckPlan of the reduced rows (DESIGN.md "Degraded flat XOR stripes").
+// Each section keeps its kernels, their argument structs and the device tables they read together
+// (PairsTable / check_map_pairs, CorrectTable / check_map_correct / xor_correct_table; the cached check
+// map of ecamd_rs.hip only owns the memory of the first two, OnceTable).  with_groups picks kernel<N> for
+// a count of load groups; stripe_grid, the grid of the stripe-by-stripe kernels, is shared with
+// ecamd_decode_masks.hip.  The extern "C" block at the end goes by operation: check, locate, pairs,
+// correct, degraded, scrub, prebuild, counters.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <array>
 #include <atomic>
-#include <map>
+#include <cstring>
 #include <memory>
-#include <mutex>
 #include <type_traits>
 #include <vector>
 
@@ -57,6 +55,30 @@
 using namespace ecamd;
 
 namespace {
+
+// One call of the driver, built once by its entry point.  suspects is null for a check and pairs for a
+// call without a pair stage, so no stage asks again what kind of call it serves.
+struct CheckCall {
+    StripeLayout lay;
+    uint32_t* status;
+    void* stream;
+    uint32_t* suspects = nullptr;
+    uint32_t* pairs = nullptr;
+    uint32_t* counts = nullptr;  // of a correcting call; may stay null
+    bool locates = false, pairs_asked = false, corrects = false;
+    int dev = 0;  // check_entry sets it
+
+    CheckCall(const void* base, int64_t stripe_stride, int64_t frag_stride, int64_t blocksize, int nstripes, uint32_t* d_status,
+              void* s)
+        : lay{static_cast<uint8_t*>(const_cast<void*>(base)), stripe_stride, frag_stride, blocksize, nstripes},
+          status(d_status), stream(s)
+    {
+    }
+    CheckCall& locate(uint32_t* d_suspects) { return locates = true, suspects = d_suspects, *this; }
+    CheckCall& pair(uint32_t* d_pairs) { return pairs_asked = true, pairs = d_pairs, *this; }
+    CheckCall& correct(uint32_t* d_counts) { return corrects = true, counts = d_counts, *this; }  // writes through lay.base
+    hipStream_t st() const { return static_cast<hipStream_t>(stream); }
+};
 
 struct CheckCmpArgs {
     const uint8_t* base;  // stored: row r of stripe s at base + s*stripe_stride + off[r]
@@ -379,49 +401,47 @@ void fill_cmask(const std::vector<int>& A, int K, int R, uint32_t* cmask)
                 if ((A[static_cast<size_t>(r) * K + j] >> b) & 1) cmask[r * 16 + b] |= 1u << j;
 }
 
-// The pair stage of one call, after locate_finalize_kernel on the same stream, which has set d_pairs
-// to 0: with R >= 4 and a table, locate_pairs_kernel and its finalize.  The grid (stripe_grid): a chunk
-// per 16 passes of 256 units -- on a clean batch the launch costs what its empty workgroups cost (11 us
-// for 16384 of them, traced).
-int locate_pairs(const std::vector<int>& A, int K, int R, const PairsTable& t, const uint8_t* base, int64_t stripe_stride,
-                 const int64_t* in_off, const int64_t* chk_off, int64_t blocksize, int nstripes, const uint32_t* d_status,
-                 const uint32_t* d_suspects, uint32_t* d_pairs, hipStream_t st)
+// What PairsArgs and CorrectArgs share, and the grid both kernels take (stripe_grid): a chunk per 16
+// passes of 256 units -- on a clean batch a launch costs what its empty workgroups cost (11 us for 16384
+// of them, traced).
+template <class Args>
+dim3 located_args(Args& a, const CheckCall& c, const std::vector<int>& A, const Participants& p, const uint32_t* table)
 {
-    if (R < 4 || R > kPairsMaxRows || !t.dev || !t.exact) return 0;
+    a.base = c.lay.base;
+    a.status = c.status;
+    a.suspects = c.suspects;
+    a.pairs = c.pairs;
+    a.table = table;
+    a.stripe_stride = c.lay.stripe_stride;
+    a.len = c.lay.blocksize;
+    std::copy(p.off, p.off + p.K + p.R, a.off);
+    fill_cmask(A, p.K, p.R, a.cmask);
+    a.nstripes = c.lay.nstripes;
+    a.K = p.K;
+    int chunks = 0, slots = 0;
+    stripe_grid((c.lay.blocksize + 3) >> 2, c.lay.nstripes, chunks, slots);
+    return dim3(static_cast<unsigned>(chunks), static_cast<unsigned>(slots));
+}
+
+// The pair stage of one call, after locate_finalize_kernel on the same stream, which has set d_pairs
+// to 0: with R >= 4 and a table, locate_pairs_kernel and its finalize.
+int locate_pairs(const CheckCall& c, const std::vector<int>& A, const Participants& p, const PairsTable& t)
+{
+    if (p.R < 4 || p.R > kPairsMaxRows || !t.dev || !t.exact) return 0;
     PairsArgs a{};
-    a.base = base;
-    a.status = d_status;
-    a.suspects = d_suspects;
-    a.pairs = d_pairs;
-    a.table = t.dev;
-    a.stripe_stride = stripe_stride;
-    a.len = blocksize;
-    for (int j = 0; j < K; j++) a.off[j] = in_off[j];
-    for (int r = 0; r < R; r++) a.off[K + r] = chk_off[r];
-    fill_cmask(A, K, R, a.cmask);
-    a.nstripes = nstripes;
-    a.K = K;
-    a.R = R;
+    const dim3 grid = located_args(a, c, A, p, t.dev), block(256);
+    a.R = p.R;
     a.singles = t.singles;
     a.npairs = t.pairs;
     a.stride = t.stride;
-    int chunks = 0, slots = 0;
-    stripe_grid((blocksize + 3) >> 2, nstripes, chunks, slots);
-    const dim3 grid(static_cast<unsigned>(chunks), static_cast<unsigned>(slots)), block(256);
-    const size_t lds = (static_cast<size_t>(R) * 256 + 1) * sizeof(uint32_t);
-    switch ((K + 3) / 4) {  // K <= 28
-    case 1: hipLaunchKernelGGL(locate_pairs_kernel<1>, grid, block, lds, st, a); break;
-    case 2: hipLaunchKernelGGL(locate_pairs_kernel<2>, grid, block, lds, st, a); break;
-    case 3: hipLaunchKernelGGL(locate_pairs_kernel<3>, grid, block, lds, st, a); break;
-    case 4: hipLaunchKernelGGL(locate_pairs_kernel<4>, grid, block, lds, st, a); break;
-    case 5: hipLaunchKernelGGL(locate_pairs_kernel<5>, grid, block, lds, st, a); break;
-    case 6: hipLaunchKernelGGL(locate_pairs_kernel<6>, grid, block, lds, st, a); break;
-    default: hipLaunchKernelGGL(locate_pairs_kernel<7>, grid, block, lds, st, a); break;
-    }
+    const size_t lds = (static_cast<size_t>(p.R) * 256 + 1) * sizeof(uint32_t);
+    with_groups<1, 7>((p.K + 3) / 4, [&](auto g) {  // K <= 28
+        hipLaunchKernelGGL(locate_pairs_kernel<decltype(g)::value>, grid, block, lds, c.st(), a);
+    });
     HIP_TRY(hipGetLastError());
     g_pairs_launches.fetch_add(1, std::memory_order_relaxed);
-    hipLaunchKernelGGL(pairs_finalize_kernel, dim3(static_cast<unsigned>((nstripes + 255) / 256)), dim3(256), 0, st, d_pairs,
-                       nstripes);
+    hipLaunchKernelGGL(pairs_finalize_kernel, dim3(static_cast<unsigned>((c.lay.nstripes + 255) / 256)), dim3(256), 0, c.st(),
+                       c.pairs, c.lay.nstripes);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -584,45 +604,24 @@ __global__ void __launch_bounds__(256) correct_counts_kernel(const uint32_t* sta
 std::atomic<long long> g_correct_launches{0};
 
 // The correction of one call, after the locate's (or the pair stage's) last kernel on the same
-// stream: correct_kernel and, with d_counts, the counts.  Nothing here waits for the stream or copies
-// to the host -- the case of every stripe is decided on the device.  The grid as locate_pairs.
-int correct_located(const std::vector<int>& A, int K, int R, const CorrectTable& t, uint8_t* base, int64_t stripe_stride,
-                    const int64_t* in_off, const int64_t* chk_off, int64_t blocksize, int nstripes, const uint32_t* d_status,
-                    const uint32_t* d_suspects, const uint32_t* d_pairs, uint32_t* d_counts, hipStream_t st)
+// stream: correct_kernel and, with counts, the counts.  Nothing here waits for the stream or copies
+// to the host -- the case of every stripe is decided on the device.  A null: nothing was checked.
+int correct_located(const CheckCall& c, const std::vector<int>* A, const Participants& p, const CorrectTable& t)
 {
-    if (R >= 1 && R <= kPairsMaxRows && t.dev) {  // no checked fragment: every stripe reads clean
+    if (p.R >= 1 && p.R <= kPairsMaxRows && t.dev) {  // no checked fragment: every stripe reads clean
         CorrectArgs a{};
-        a.base = base;
-        a.status = d_status;
-        a.suspects = d_suspects;
-        a.pairs = t.pairs ? d_pairs : nullptr;
-        a.table = t.dev;
-        a.stripe_stride = stripe_stride;
-        a.len = blocksize;
-        for (int j = 0; j < K; j++) a.off[j] = in_off[j];
-        for (int r = 0; r < R; r++) a.off[K + r] = chk_off[r];
-        fill_cmask(A, K, R, a.cmask);
-        a.nstripes = nstripes;
-        a.K = K;
-        a.P = K + R;
-        int chunks = 0, slots = 0;
-        stripe_grid((blocksize + 3) >> 2, nstripes, chunks, slots);
-        const dim3 grid(static_cast<unsigned>(chunks), static_cast<unsigned>(slots)), block(256);
-        switch ((K + 3) / 4) {  // K <= 31
-        case 1: hipLaunchKernelGGL(correct_kernel<1>, grid, block, 0, st, a); break;
-        case 2: hipLaunchKernelGGL(correct_kernel<2>, grid, block, 0, st, a); break;
-        case 3: hipLaunchKernelGGL(correct_kernel<3>, grid, block, 0, st, a); break;
-        case 4: hipLaunchKernelGGL(correct_kernel<4>, grid, block, 0, st, a); break;
-        case 5: hipLaunchKernelGGL(correct_kernel<5>, grid, block, 0, st, a); break;
-        case 6: hipLaunchKernelGGL(correct_kernel<6>, grid, block, 0, st, a); break;
-        case 7: hipLaunchKernelGGL(correct_kernel<7>, grid, block, 0, st, a); break;
-        default: hipLaunchKernelGGL(correct_kernel<8>, grid, block, 0, st, a); break;
-        }
+        const dim3 grid = located_args(a, c, *A, p, t.dev), block(256);
+        if (!t.pairs) a.pairs = nullptr;
+        a.P = p.K + p.R;
+        with_groups<1, 8>((p.K + 3) / 4, [&](auto g) {  // K <= 31
+            hipLaunchKernelGGL(correct_kernel<decltype(g)::value>, grid, block, 0, c.st(), a);
+        });
         HIP_TRY(hipGetLastError());
         g_correct_launches.fetch_add(1, std::memory_order_relaxed);
     }
-    if (d_counts) {
-        hipLaunchKernelGGL(correct_counts_kernel, dim3(1), dim3(256), 0, st, d_status, d_suspects, d_pairs, nstripes, d_counts);
+    if (c.counts) {
+        hipLaunchKernelGGL(correct_counts_kernel, dim3(1), dim3(256), 0, c.st(), c.status, c.suspects, c.pairs, c.lay.nstripes,
+                           c.counts);
         HIP_TRY(hipGetLastError());
     }
     return 0;
@@ -754,28 +753,47 @@ __global__ void __launch_bounds__(256) xor_check_kernel(const Args a)
 
 std::atomic<long long> g_xor_check_fused{0}, g_xor_locate_fused{0};
 
-template <bool LOCATE, class Args>
-void xor_check_launch(int groups, dim3 grid, dim3 block, hipStream_t st, const Args& a)
+// The slots of a degraded flat XOR plan (ecamd_xor_check_plan_degraded), what the degraded form of
+// xor_check_kernel works on: the participants -- the available fragments that occur in a surviving row,
+// ascending -- and the surviving rows packed densely in the order of their owners, the checked fragments.
+struct XorSlots {
+    std::vector<int> frag;        // fragment index of slot i
+    std::vector<uint32_t> masks;  // packed row r over slot numbers
+    std::vector<uint32_t> sig;    // slot i over packed rows
+};
+
+// What the entry points differ in: who takes part, the map between them, and which kernel takes the
+// whole tiles.  Made in place by its family's builder and not copied (A may point into it).
+enum class Fused { kNone, kRsBitsliced, kXorFull, kXorSlots };
+struct CheckPlan {
+    Fused fused = Fused::kNone;
+    int K = 0, R = 0;
+    uint8_t frag[32] = {};                // fragment index of input j at [j], of checked row r at [K + r]
+    const std::vector<int>* A = nullptr;  // R x K over GF(2^16): checked row r = sum of A[r][j] * input j (null: R == 0)
+    // rs_vand: the cached check map, what A points into; its map computes the checked rows in the generic stage
+    CheckMap cached;
+    // flat XOR: the rows over the inputs as 0 / 1, what A points to; the generic stage takes them as masks
+    std::vector<int> bitmaps;
+    std::vector<uint32_t> sig;  // kXorFull: the signatures of ecamd_xor_check_plan
+    XorSlots slots;             // kXorSlots
+    PairsTable pairs;           // ecamd_rs_locate_pairs
+    CorrectTable correct;       // a correcting call
+    CheckPlan() = default;
+    CheckPlan(const CheckPlan&) = delete;
+    CheckPlan& operator=(const CheckPlan&) = delete;
+    void input(int f) { frag[K++] = static_cast<uint8_t>(f); }  // all of them before the first checked row
+    void checked(int f) { frag[K + R++] = static_cast<uint8_t>(f); }
+};
+
+// Row r of the 0 / 1 matrix A (R x K) as a mask over its K inputs.
+uint32_t row_mask(const std::vector<int>& A, int K, int r)
 {
-    // full stripes: 2 ((3,3,3): 6 fragments) to 7 ((20,6,4): 26); degraded: 1 (up to 4 participants) to 7
-    switch (groups) {
-    case 1:
-        if constexpr (std::is_same_v<Args, XorCheckSlotArgs>) {
-            hipLaunchKernelGGL((xor_check_kernel<1, LOCATE, Args>), grid, block, 0, st, a);
-            break;
-        }
-        [[fallthrough]];
-    case 2: hipLaunchKernelGGL((xor_check_kernel<2, LOCATE, Args>), grid, block, 0, st, a); break;
-    case 3: hipLaunchKernelGGL((xor_check_kernel<3, LOCATE, Args>), grid, block, 0, st, a); break;
-    case 4: hipLaunchKernelGGL((xor_check_kernel<4, LOCATE, Args>), grid, block, 0, st, a); break;
-    case 5: hipLaunchKernelGGL((xor_check_kernel<5, LOCATE, Args>), grid, block, 0, st, a); break;
-    case 6: hipLaunchKernelGGL((xor_check_kernel<6, LOCATE, Args>), grid, block, 0, st, a); break;
-    default: hipLaunchKernelGGL((xor_check_kernel<7, LOCATE, Args>), grid, block, 0, st, a); break;
-    }
+    uint32_t v = 0;
+    for (int j = 0; j < K; j++) v |= static_cast<uint32_t>(A[static_cast<size_t>(r) * K + j] & 1) << j;
+    return v;
 }
 
-// Fused stage of ecamd_xor_check or, with d_suspects, of ecamd_xor_locate over the whole tiles of
-// every fragment (fragment f at f*frag_stride; masks: the m parity bitmaps, sig: ecamd_xor_check_plan).
+// Fused stage of a flat XOR check or, with suspects, locate over the whole tiles of every fragment.
 // Geometry as launch_xor: one-wave workgroups on 1 KiB tiles or 256-lane workgroups on 4 KiB tiles
 // (knob xor_check_threads 64 / 256), one workgroup per tile, long batches as launches of
 // xor_tiles_per_slot tiles (of 4 KiB) per slot with xor_wgs (0: 3) slots per CU.  By default one-wave
@@ -785,83 +803,75 @@ void xor_check_launch(int groups, dim3 grid, dim3 block, hipStream_t st, const A
 // the bytes of each fragment covered, or 0 with nothing launched when it declines: knob
 // xor_check_fused 0, a fragment shorter than a tile, a stripe the 32-bit buffer offsets cannot span.
 // xor_check_tiles is the part both argument forms share: `a` comes with its tables filled, `last` is the
-// highest fragment index it loads.
+// highest fragment index it loads.  Load groups -- full stripes: 2 ((3,3,3): 6 fragments) to 7 ((20,6,4):
+// 26); degraded: 1 (up to 4 participants) to 7.
 template <class Args>
-int64_t xor_check_tiles(int dev, Args& a, int last, const uint8_t* base, int64_t stripe_stride, int64_t frag_stride,
-                        int64_t blocksize, int nstripes, uint32_t* d_status, uint32_t* d_suspects, void* stream)
+int64_t xor_check_tiles(const CheckCall& c, Args& a, int last)
 {
     constexpr bool kSlots = std::is_same_v<Args, XorCheckSlotArgs>;
-    if (!g_tune.xor_check_fused || nstripes <= 0) return 0;
+    const StripeLayout& l = c.lay;
+    if (!g_tune.xor_check_fused || l.nstripes <= 0) return 0;
     const int knob_threads = g_tune.xor_check_threads;
     const int threads = knob_threads ? knob_threads : 64;
     const int64_t tile = static_cast<int64_t>(threads) * 16;
-    const int64_t cover = blocksize / tile * tile;
-    if (cover == 0 || stripe_stride < 0) return 0;
-    if (last * frag_stride + blocksize >= (int64_t(1) << 31)) return 0;
+    const int64_t cover = l.blocksize / tile * tile;
+    if (cover == 0 || l.stripe_stride < 0) return 0;
+    if (last * l.frag_stride + l.blocksize >= (int64_t(1) << 31)) return 0;
     const uint64_t tps = static_cast<uint64_t>(cover / tile);
     const int wgs_knob = g_tune.xor_wgs;
     const int wgs = wgs_knob > 0 ? wgs_knob : 3;
-    const uint64_t slots = static_cast<uint64_t>(dev_cu_count(dev)) * static_cast<uint64_t>(wgs);
+    const uint64_t slots = static_cast<uint64_t>(dev_cu_count(c.dev)) * static_cast<uint64_t>(wgs);
     const uint64_t limit = static_cast<uint64_t>(std::max<int>(g_tune.xor_tiles_per_slot, 0)) * static_cast<uint64_t>(256 / threads);
-    const int per = launch_stripes(nstripes, tps, slots, limit);
+    const int per = launch_stripes(l.nstripes, tps, slots, limit);
     if (tps * static_cast<uint64_t>(per) > 0x7fffffffull) return 0;
-    a.stripe_stride = stripe_stride;
-    a.records = static_cast<uint32_t>(last * frag_stride + cover);
+    a.stripe_stride = l.stripe_stride;
+    a.records = static_cast<uint32_t>(last * l.frag_stride + cover);
     a.tiles_per_stripe = static_cast<uint32_t>(tps);
     for (int i = 0; i < a.nfrags; i++) {
         int f = i;
         if constexpr (kSlots) f = a.slot_frag[i];
-        a.off32[i] = static_cast<int32_t>(f * frag_stride);
+        a.off32[i] = static_cast<int32_t>(f * l.frag_stride);
     }
-    const int groups = (a.nfrags + 3) / 4;
-    const auto st = static_cast<hipStream_t>(stream);
-    for (int s0 = 0; s0 < nstripes; s0 += per) {
-        const int ns = std::min(per, nstripes - s0);
-        a.base = base + s0 * stripe_stride;
-        a.status = d_status + s0;
-        a.suspects = d_suspects ? d_suspects + s0 : nullptr;
+    const bool locate = c.suspects != nullptr;
+    for (int s0 = 0; s0 < l.nstripes; s0 += per) {
+        const int ns = std::min(per, l.nstripes - s0);
+        a.base = l.base + s0 * l.stripe_stride;
+        a.status = c.status + s0;
+        a.suspects = locate ? c.suspects + s0 : nullptr;
         const dim3 grid(static_cast<unsigned>(tps * static_cast<uint64_t>(ns))), block(static_cast<unsigned>(threads));
-        if (d_suspects)
-            xor_check_launch<true>(groups, grid, block, st, a);
-        else
-            xor_check_launch<false>(groups, grid, block, st, a);
+        with_groups<kSlots ? 1 : 2, 7>((a.nfrags + 3) / 4, [&](auto g) {
+            if (locate)
+                hipLaunchKernelGGL((xor_check_kernel<decltype(g)::value, true, Args>), grid, block, 0, c.st(), a);
+            else
+                hipLaunchKernelGGL((xor_check_kernel<decltype(g)::value, false, Args>), grid, block, 0, c.st(), a);
+        });
         HIP_TRY(hipGetLastError());
-        (d_suspects ? g_xor_locate_fused : g_xor_check_fused).fetch_add(1, std::memory_order_relaxed);
+        (locate ? g_xor_locate_fused : g_xor_check_fused).fetch_add(1, std::memory_order_relaxed);
     }
     return cover;
 }
 
-int64_t xor_check_fused(int dev, int k, int m, const uint32_t* masks, const uint32_t* sig, const uint8_t* base,
-                        int64_t stripe_stride, int64_t frag_stride, int64_t blocksize, int nstripes, uint32_t* d_status,
-                        uint32_t* d_suspects, void* stream)
+// Full stripes: fragment f of the k + m at f*frag_stride, row r the parity bitmap with the stored parity
+// folded in.
+int64_t xor_check_fused(const CheckCall& c, const CheckPlan& p)
 {
-    const int n = k + m;
+    const int k = p.K, m = p.R, n = k + m;
     if (n <= 4 || n > kXorCheckMaxFrags || m > kXorCheckMaxRows) return 0;
     XorCheckArgs a{};
     a.nfrags = n;
     a.nrows = m;
     a.k = k;
-    for (int f = 0; f < n; f++) a.sig[f] = sig[f];
-    for (int p = 0; p < m; p++) a.masks[p] = masks[p] | (1u << (k + p));
-    return xor_check_tiles(dev, a, n - 1, base, stripe_stride, frag_stride, blocksize, nstripes, d_status, d_suspects, stream);
+    for (int f = 0; f < n; f++) a.sig[f] = p.sig[static_cast<size_t>(f)];
+    for (int r = 0; r < m; r++) a.masks[r] = row_mask(*p.A, k, r) | (1u << (k + r));
+    return xor_check_tiles(c, a, n - 1);
 }
-
-// The slots of a degraded flat XOR plan (ecamd_xor_check_plan_degraded), what the degraded form of xor_check_kernel
-// works on: the participants -- the available fragments that occur in a surviving row, ascending --
-// and the surviving rows packed densely in the order of their owners.
-struct XorSlots {
-    std::vector<int> frag;        // fragment index of slot i
-    std::vector<uint32_t> masks;  // packed row r over slot numbers
-    std::vector<uint32_t> sig;    // slot i over packed rows
-    std::vector<int> row_bit;     // status bit of packed row r: k + its owner
-};
 
 // The same stage for a degraded stripe: only the participants are loaded, in (participants + 3) / 4
 // groups.  Declines as xor_check_fused does, and for a plan without a surviving row.
-int64_t xor_check_fused_slots(int dev, const XorSlots& sl, const uint8_t* base, int64_t stripe_stride, int64_t frag_stride,
-                              int64_t blocksize, int nstripes, uint32_t* d_status, uint32_t* d_suspects, void* stream)
+int64_t xor_check_fused_slots(const CheckCall& c, const CheckPlan& p)
 {
-    const int n = static_cast<int>(sl.frag.size()), rows = static_cast<int>(sl.masks.size());
+    const XorSlots& sl = p.slots;
+    const int n = static_cast<int>(sl.frag.size()), rows = p.R;
     if (n < 1 || n > kXorCheckMaxFrags || rows < 1 || rows > kXorCheckMaxRows) return 0;
     XorCheckSlotArgs a{};
     a.nfrags = n;
@@ -872,43 +882,23 @@ int64_t xor_check_fused_slots(int dev, const XorSlots& sl, const uint8_t* base, 
     }
     for (int r = 0; r < rows; r++) {
         a.masks[r] = sl.masks[static_cast<size_t>(r)];
-        a.row_bit[r] = static_cast<uint8_t>(sl.row_bit[static_cast<size_t>(r)]);
+        a.row_bit[r] = p.frag[p.K + r];
     }
-    return xor_check_tiles(dev, a, sl.frag.back(), base, stripe_stride, frag_stride, blocksize, nstripes, d_status, d_suspects,
-                           stream);
+    return xor_check_tiles(c, a, sl.frag.back());
 }
 
-// What the entry points differ in.  Fragment f of stripe s lies at base + s*stripe_stride +
-// f*frag_stride.
-struct CheckPlan {
-    std::vector<int> inputs, checked;     // fragment indices of the K inputs and the R checked fragments
-    const std::vector<int>* A = nullptr;  // R x K over GF(2^16): checked row r = sum of A[r][j] * input j
-    // what computes the checked rows into the scratch
-    const ecamd_map* map = nullptr;  // rs_vand: ecamd_map_apply_strided; whole tiles take the fused stage
-    std::vector<uint32_t> masks;     // flat XOR: ecamd_xor_apply_strided over the parity bitmaps; whole tiles take
-    std::vector<uint32_t> sig;       //   xor_check_fused with the signatures of ecamd_xor_check_plan
-    CheckMap cached;                 // what A and map point into: the cached check map (rs_vand)
-    PairsTable pairs;                //   and its pair table (ecamd_rs_locate_pairs)
-    CorrectTable correct;            // the correction table (ecamd_rs_correct: with the cached map; flat XOR: xor_correct_table)
-    std::vector<int> bitmaps;        // or the parity bitmaps as 0 / 1 (flat XOR)
-    // flat XOR with fragments missing (xor_degraded_call): masks and bitmaps are the reduced rows over
-    // `inputs`, sig stays empty and whole tiles take xor_check_fused_slots over these
-    bool degraded = false;
-    XorSlots slots;
-};
-
-// Bytes [from, bs) of the checked fragments at off[] (bit bits[r] each) of every stripe against what
-// the plan's apply computes from the inputs at in_off[].  `from` a multiple of 16.  With `loc` (its
-// map tables, input bits and suspects filled in) the compare step is locate_compare_kernel, which
-// writes the status bits too.
-int check_generic(int dev, void* stream, const CheckPlan& p, const uint8_t* base, int64_t stripe_stride,
-                  const int64_t* in_off, const int64_t* off, const uint8_t* bits, int64_t from, int64_t bs, int nstripes,
-                  uint32_t* d_status, const LocateCmpArgs* loc)
+// Generic stage: bytes [from, blocksize) of the checked rows of every stripe against what the plan's
+// apply computes from the inputs.  `from` a multiple of 16.  With `loc` (its map tables, input bits
+// and suspects filled in) the compare step is locate_compare_kernel, which writes the status bits too.
+int check_generic(const CheckCall& c, const CheckPlan& p, const Participants& pt, int64_t from, const LocateCmpArgs* loc)
 {
-    const int nrows = static_cast<int>(p.checked.size());
+    const StripeLayout& l = c.lay;
+    const int nrows = pt.R, nstripes = l.nstripes;
+    const int64_t bs = l.blocksize;
     if (from >= bs || nrows <= 0 || nstripes <= 0) return 0;
-    if (nrows > 32) return dev_fail(ECAMD_EINVAL, "check of %d fragments", nrows);
-    const auto st = static_cast<hipStream_t>(stream);
+    std::vector<uint32_t> masks;  // flat XOR: ecamd_xor_apply_strided over the rows of A
+    if (!p.cached.map)
+        for (int r = 0; r < nrows; r++) masks.push_back(row_mask(*p.A, pt.K, r));
     const int64_t cap = static_cast<int64_t>(kCheckScratchBytes);
     const int64_t seg = std::max<int64_t>(65536, cap / nrows / 65536 * 65536);  // fragment bytes per pass
     for (int64_t f0 = from; f0 < bs; f0 += seg) {
@@ -916,45 +906,44 @@ int check_generic(int dev, void* stream, const CheckPlan& p, const uint8_t* base
         const int64_t pitch = (len + 255) & ~int64_t(255);
         const int per = static_cast<int>(std::min<int64_t>(std::clamp<int64_t>(cap / (pitch * nrows), 1, 65535), nstripes));
         uint32_t* scratch = nullptr;
-        int rc = stream_scratch(dev, stream, kCheckScratchSlot, static_cast<size_t>(per) * nrows * pitch / 4, &scratch);
+        int rc = stream_scratch(c.dev, c.stream, kCheckScratchSlot, static_cast<size_t>(per) * nrows * pitch / 4, &scratch);
         if (rc) return rc;
         auto* calc = reinterpret_cast<uint8_t*>(scratch);
-        std::vector<int64_t> io(in_off, in_off + p.inputs.size()), oo;
+        std::vector<int64_t> io(pt.off, pt.off + pt.K), oo;
         for (auto& v : io) v += f0;
         for (int r = 0; r < nrows; r++) oo.push_back(r * pitch);
         for (int s0 = 0; s0 < nstripes; s0 += per) {
             const int ns = std::min(per, nstripes - s0);
-            const uint8_t* in = base + s0 * stripe_stride;
-            rc = p.map ? ecamd_map_apply_strided(p.map, in, stripe_stride, io.data(), calc, nrows * pitch, oo.data(), len, ns, stream)
-                       : ecamd_xor_apply_strided(p.masks.data(), nrows, static_cast<int>(io.size()), in, stripe_stride, io.data(),
-                                                 calc, nrows * pitch, oo.data(), len, ns, stream);
+            const uint8_t* in = l.base + s0 * l.stripe_stride;
+            rc = p.cached.map ? ecamd_map_apply_strided(p.cached.map, in, l.stripe_stride, io.data(), calc, nrows * pitch, oo.data(),
+                                                        len, ns, c.stream)
+                              : ecamd_xor_apply_strided(masks.data(), nrows, pt.K, in, l.stripe_stride, io.data(), calc,
+                                                        nrows * pitch, oo.data(), len, ns, c.stream);
             if (rc) return rc;
             // the fields both compare kernels take
             auto common = [&](auto& a, uint8_t* row_bit) {
-                a.base = base + s0 * stripe_stride + f0;
+                a.base = in + f0;
                 a.calc = calc;
-                a.status = d_status + s0;
-                a.stripe_stride = stripe_stride;
+                a.status = c.status + s0;
+                a.stripe_stride = l.stripe_stride;
                 a.pitch = pitch;
                 a.len = len;
                 a.nrows = nrows;
-                for (int r = 0; r < nrows; r++) {
-                    a.off[r] = off[r];
-                    row_bit[r] = bits[r];
-                }
+                std::copy(pt.off + pt.K, pt.off + pt.K + nrows, a.off);
+                std::copy(pt.bit + pt.K, pt.bit + pt.K + nrows, row_bit);
             };
             if (loc) {
-                LocateCmpArgs l = *loc;
-                common(l, l.row_bit);
-                l.suspects = loc->suspects + s0;
+                LocateCmpArgs la = *loc;
+                common(la, la.row_bit);
+                la.suspects = loc->suspects + s0;
                 const unsigned lx = static_cast<unsigned>(std::clamp<int64_t>((((len + 15) >> 4) + 1023) / 1024, 1, 1024));
-                hipLaunchKernelGGL(locate_compare_kernel, dim3(lx, static_cast<unsigned>(ns)), dim3(256), 0, st, l);
+                hipLaunchKernelGGL(locate_compare_kernel, dim3(lx, static_cast<unsigned>(ns)), dim3(256), 0, c.st(), la);
             } else {
-                CheckCmpArgs c{};
-                common(c, c.bit);
+                CheckCmpArgs ca{};
+                common(ca, ca.bit);
                 const unsigned gx = static_cast<unsigned>(std::clamp<int64_t>(((len >> 4) + 1023) / 1024, 1, 1024));
                 hipLaunchKernelGGL(check_compare_kernel, dim3(gx, static_cast<unsigned>(nrows), static_cast<unsigned>(ns)),
-                                   dim3(256), 0, st, c);
+                                   dim3(256), 0, c.st(), ca);
             }
             HIP_TRY(hipGetLastError());
         }
@@ -962,18 +951,16 @@ int check_generic(int dev, void* stream, const CheckPlan& p, const uint8_t* base
     return 0;
 }
 
-// The layout checks of every entry point and, for a locate, its own two.
-int check_layout(bool locate, const void* base, int64_t stripe_stride, int64_t frag_stride, int64_t blocksize,
-                 int nstripes, const uint32_t* d_status, const uint32_t* d_suspects)
+// The layout checks of every entry point, a locate's own two, and the pair stage's.
+int check_layout(const CheckCall& c)
 {
-    if (!base || !d_status || nstripes < 0 || blocksize < 1 || frag_stride < blocksize)
-        return dev_fail(ECAMD_EINVAL, "bad base / status / blocksize / strides");
-    if ((reinterpret_cast<uintptr_t>(base) & 15u) || stripe_stride % 16 || frag_stride % 16)
-        return dev_fail(ECAMD_EINVAL, "fragment addresses must be 16-byte aligned");
-    if (locate && !d_suspects) return dev_fail(ECAMD_EINVAL, "null suspects");
+    if (!c.lay.sane() || !c.status) return dev_fail(ECAMD_EINVAL, "bad base / status / blocksize / strides");
+    if (!c.lay.aligned16()) return dev_fail(ECAMD_EINVAL, "fragment addresses must be 16-byte aligned");
+    if (c.locates && !c.suspects) return dev_fail(ECAMD_EINVAL, "null suspects");
     // an odd size ends in half a word, whose product is cut to 8 bits: proportionality cannot be tested
-    if (locate && (blocksize & 1))
-        return dev_fail(ECAMD_EINVAL, "locate needs an even blocksize (%lld)", static_cast<long long>(blocksize));
+    if (c.locates && (c.lay.blocksize & 1))
+        return dev_fail(ECAMD_EINVAL, "locate needs an even blocksize (%lld)", static_cast<long long>(c.lay.blocksize));
+    if (c.pairs_asked && !c.pairs) return dev_fail(ECAMD_EINVAL, "null pairs");
     return 0;
 }
 
@@ -1002,84 +989,72 @@ void locate_tables(const std::vector<int>& A, int R, int K, LocateCmpArgs& l)
     }
 }
 
-// The check (d_suspects null) or locate of one validated call: both arrays set, the fused stage over
-// whole tiles, the generic stage over the rest, the finalize step of a locate and, with d_pairs, the
-// pair stage on its results and, with fix_base (the same address as base, writable: ecamd_rs_correct,
-// ecamd_xor_correct), the correction on both.  StreamUse: the scratch of the stream context outlives
-// the call.
-int run_check(int dev, const CheckPlan& p, const void* base, int64_t stripe_stride, int64_t frag_stride,
-              int64_t blocksize, int nstripes, uint32_t* d_status, uint32_t* d_suspects, void* stream,
-              uint32_t* d_pairs = nullptr, void* fix_base = nullptr, uint32_t* d_counts = nullptr)
+// One validated call: both arrays set, the fused stage over whole tiles, the generic stage over the
+// rest, the finalize step of a locate, the pair stage on its results and the correction on both.
+// StreamUse: the scratch of the stream context outlives the call.
+int run_check(const CheckCall& c, const CheckPlan& p)
 {
-    if (nstripes == 0) return 0;
-    const StreamUse use(dev, stream);
-    const auto st = static_cast<hipStream_t>(stream);
-    const size_t words = static_cast<size_t>(nstripes) * sizeof(uint32_t);
-    if (d_suspects) HIP_TRY(hipMemsetAsync(d_suspects, 0xff, words, st));
-    HIP_TRY(hipMemsetAsync(d_status, 0, words, st));
-    const int K = static_cast<int>(p.inputs.size()), R = static_cast<int>(p.checked.size());
-    const auto* b = static_cast<const uint8_t*>(base);
-    std::vector<int64_t> in_off, chk_off;
-    std::vector<uint8_t> in_bits, bits;
-    uint32_t participating = 0;
-    for (int i : p.inputs) {
-        in_off.push_back(i * frag_stride);
-        in_bits.push_back(static_cast<uint8_t>(i));
-        participating |= 1u << i;
+    const StripeLayout& l = c.lay;
+    if (l.nstripes == 0) return 0;
+    const StreamUse use(c.dev, c.stream);
+    const size_t words = static_cast<size_t>(l.nstripes) * sizeof(uint32_t);
+    if (c.suspects) HIP_TRY(hipMemsetAsync(c.suspects, 0xff, words, c.st()));
+    HIP_TRY(hipMemsetAsync(c.status, 0, words, c.st()));
+    const int K = p.K, R = p.R;
+    Participants pt;
+    pt.K = K;
+    pt.R = R;
+    for (int i = 0; i < K + R; i++) {
+        pt.bit[i] = p.frag[i];
+        pt.off[i] = p.frag[i] * l.frag_stride;
+        pt.mask |= 1u << p.frag[i];
     }
-    for (int f : p.checked) {
-        chk_off.push_back(f * frag_stride);
-        bits.push_back(static_cast<uint8_t>(f));
-        participating |= 1u << f;
-    }
-    // fewer than 2 checked fragments tell nothing apart: the check, then every participating
-    // fragment of a dirty stripe
-    const bool locating = d_suspects && R >= 2;
-    auto fused = [&](int row0, int nrows) {
-        return check_fused(dev, *p.A, K, row0, nrows, b, stripe_stride, in_off.data(), chk_off.data(), bits.data(), d_status,
-                           locating ? d_suspects : nullptr, in_bits.data(), blocksize, nstripes, stream);
-    };
+    // fewer than 2 checked fragments tell nothing apart: the two stages run as a check, then the finalize
+    // names every participating fragment of a dirty stripe
+    CheckCall stage = c;
+    if (R < 2) stage.suspects = nullptr;
+    const bool locating = stage.suspects != nullptr;
     // whole tiles through the fused kernel; what it covered is done, the rest of each fragment goes
     // the generic way
     int64_t cover = 0;
-    if (p.map && locating) {
-        // one launch over all R rows: the second stage needs every row's syndrome in one wave, so
-        // more than 8 rows are declined and take the generic stage alone
-        cover = fused(0, R);
-    } else if (p.map) {
-        // one launch per group of 8 rows; only what EVERY group covered is done
-        cover = blocksize;
-        for (int row0 = 0; row0 < R && cover >= 0; row0 += 8) cover = std::min(cover, fused(row0, std::min(8, R - row0)));
-    } else if (!p.sig.empty()) {
-        // flat XOR: one launch reads all K + R fragments of a tile and takes the syndromes from the loads
-        cover = xor_check_fused(dev, K, R, p.masks.data(), p.sig.data(), b, stripe_stride, frag_stride, blocksize, nstripes,
-                                d_status, locating ? d_suspects : nullptr, stream);
-    } else if (p.degraded) {
-        // the same over the participants of the reduced rows alone
-        cover = xor_check_fused_slots(dev, p.slots, b, stripe_stride, frag_stride, blocksize, nstripes, d_status,
-                                      locating ? d_suspects : nullptr, stream);
+    switch (p.fused) {
+    case Fused::kRsBitsliced:
+        if (locating) {
+            // one launch over all R rows: the second stage needs every row's syndrome in one wave, so
+            // more than 8 rows are declined and take the generic stage alone
+            cover = check_fused(c.dev, *p.A, pt, 0, R, l, c.status, c.suspects, c.stream);
+        } else {
+            // one launch per group of 8 rows; only what EVERY group covered is done
+            cover = l.blocksize;
+            for (int row0 = 0; row0 < R && cover >= 0; row0 += 8)
+                cover = std::min(cover, check_fused(c.dev, *p.A, pt, row0, std::min(8, R - row0), l, c.status, nullptr, c.stream));
+        }
+        break;
+    case Fused::kXorFull:  // one launch reads all K + R fragments of a tile and takes the syndromes from the loads
+        cover = xor_check_fused(stage, p);
+        break;
+    case Fused::kXorSlots:  // the same over the participants of the reduced rows alone
+        cover = xor_check_fused_slots(stage, p);
+        break;
+    case Fused::kNone: break;
     }
     if (cover < 0) return static_cast<int>(cover);
     LocateCmpArgs loc{};
     if (locating) {
-        loc.suspects = d_suspects;
+        loc.suspects = c.suspects;
         locate_tables(*p.A, R, K, loc);
-        for (int j = 0; j < K; j++) loc.in_bit[j] = in_bits[static_cast<size_t>(j)];
+        std::copy(pt.bit, pt.bit + K, loc.in_bit);
     }
-    const int rc = check_generic(dev, stream, p, b, stripe_stride, in_off.data(), chk_off.data(), bits.data(), cover,
-                                 blocksize, nstripes, d_status, locating ? &loc : nullptr);
-    if (rc || !d_suspects) return rc;
-    hipLaunchKernelGGL(locate_finalize_kernel, dim3(static_cast<unsigned>((nstripes + 255) / 256)), dim3(256), 0, st,
-                       d_status, d_suspects, participating, nstripes, d_pairs);
+    const int rc = check_generic(stage, p, pt, cover, locating ? &loc : nullptr);
+    if (rc || !c.suspects) return rc;
+    hipLaunchKernelGGL(locate_finalize_kernel, dim3(static_cast<unsigned>((l.nstripes + 255) / 256)), dim3(256), 0, c.st(),
+                       c.status, c.suspects, pt.mask, l.nstripes, c.pairs);
     HIP_TRY(hipGetLastError());
-    if (d_pairs && R >= 4) {  // fewer than four checks leave d_pairs zero
-        const int prc = locate_pairs(*p.A, K, R, p.pairs, b, stripe_stride, in_off.data(), chk_off.data(), blocksize, nstripes,
-                                     d_status, d_suspects, d_pairs, st);
+    if (c.pairs && R >= 4) {  // fewer than four checks leave d_pairs zero
+        const int prc = locate_pairs(c, *p.A, pt, p.pairs);
         if (prc) return prc;
     }
-    if (!fix_base) return 0;
-    return correct_located(*p.A, K, R, p.correct, static_cast<uint8_t*>(fix_base), stripe_stride, in_off.data(), chk_off.data(),
-                           blocksize, nstripes, d_status, d_suspects, d_pairs, d_counts, st);
+    return c.corrects ? correct_located(c, p.A, pt, p.correct) : 0;
 }
 
 // The pair table of a cached check map (PairsTable above), made at the first call that asks for it and
@@ -1179,187 +1154,182 @@ int check_map_correct(const CheckMap& cm, CorrectTable& out)
     return 0;
 }
 
-// ecamd_rs_check (locate false), ecamd_rs_locate and ecamd_rs_locate_pairs (pairs true): a bad layout
-// is reported before too many missing fragments, so it is checked before the plan is made.
-int rs_call(bool locate, int k, int m, const int* missing, const void* base, int64_t stripe_stride, int64_t frag_stride,
-            int64_t blocksize, int nstripes, uint32_t* d_status, uint32_t* d_suspects, uint32_t* checked, void* stream,
-            bool pairs = false, uint32_t* d_pairs = nullptr, void* fix_base = nullptr, uint32_t* d_counts = nullptr)
-{
-    int dev = 0;
-    int rc = dev_ensure(&dev);
-    if (rc) return rc;
-    if (k <= 0 || m < 0 || k + m > 32)
-        return dev_fail(ECAMD_EINVAL, "%s needs k + m <= 32 (k=%d m=%d)", locate ? "locate" : "check", k, m);
-    if ((rc = check_layout(locate, base, stripe_stride, frag_stride, blocksize, nstripes, d_status, d_suspects))) return rc;
-    if (pairs && !d_pairs) return dev_fail(ECAMD_EINVAL, "null pairs");
-    CheckPlan p;
-    if ((rc = check_map(k, m, missing, p.cached))) return rc;
-    if (pairs && (rc = check_map_pairs(p.cached, p.pairs))) return rc;
-    if (fix_base && (rc = check_map_correct(p.cached, p.correct))) return rc;
-    p.inputs = *p.cached.inputs;
-    p.checked = *p.cached.checked;
-    p.A = p.cached.coeff;
-    p.map = p.cached.map;
-    uint32_t mask = 0;
-    for (int f : p.checked) mask |= 1u << f;
-    if (checked) *checked = mask;  // for an empty batch too
-    return run_check(dev, p, base, stripe_stride, frag_stride, blocksize, nstripes, d_status, locate ? d_suspects : nullptr,
-                     stream, pairs ? d_pairs : nullptr, fix_base, d_counts);
-}
-
 // The correction table of a flat XOR code (CorrectTable above) from its check plan:
 // fragment f is participant f, its pivot the lowest row of sig[f], every scale 1.  Device memory made
 // at the first call that asks, per (device, k, m, hd, mask of lost fragments), and kept for the life of
 // the process (a few accepted codes and the loss patterns a caller meets, 128 bytes each).  With
-// fragments lost (`plan` degraded) fragment f is the participant correct_kernel loads in its place --
-// its index among plan.inputs, or K + r for the owner of packed row r -- and its pivot the packed row
-// of the lowest bit of sig[f]; a fragment no surviving row contains takes no part.
-int xor_correct_table(int dev, int k, int m, int hd, uint32_t lost, const std::vector<uint32_t>& sig, const CheckPlan& plan,
-                      CorrectTable& out)
+// fragments lost (a kXorSlots plan) fragment f is the participant correct_kernel loads in its place --
+// its index among the plan's inputs, or K + r for the owner of packed row r -- and its pivot the packed
+// row of the lowest bit of sig[f]; a fragment no surviving row contains takes no part.
+int xor_correct_table(int dev, int k, int m, int hd, uint32_t lost, const unsigned* sig, const CheckPlan& plan, CorrectTable& out)
 {
-    static std::mutex mu;
-    static std::map<std::array<int, 5>, const uint32_t*> tables;
-    const std::lock_guard<std::mutex> lk(mu);
-    const uint32_t*& slot = tables[{dev, k, m, hd, static_cast<int>(lost)}];
-    if (!slot) {
+    static CodeTables<5> tables("correction table");
+    const void* d = nullptr;
+    const int rc = tables.get({dev, k, m, hd, static_cast<int>(lost)}, [&](std::vector<uint8_t>& bytes) {
         uint32_t tab[32];
         for (int f = 0; f < 32; f++)
-            tab[f] = f < k + m && sig[static_cast<size_t>(f)]
-                         ? static_cast<uint32_t>(f) | static_cast<uint32_t>(__builtin_ctz(sig[static_cast<size_t>(f)])) << 8 | 1u << 16
-                         : 0xffffffffu;
-        if (plan.degraded) {
-            const int K = static_cast<int>(plan.inputs.size()), R = static_cast<int>(plan.checked.size());
+            tab[f] = f < k + m && sig[f] ? static_cast<uint32_t>(f) | static_cast<uint32_t>(__builtin_ctz(sig[f])) << 8 | 1u << 16
+                                         : 0xffffffffu;
+        if (plan.fused == Fused::kXorSlots) {
+            const uint8_t* inputs = plan.frag;
+            const uint8_t* checked = plan.frag + plan.K;
             for (int f = 0; f < k + m; f++) {
                 if (tab[f] == 0xffffffffu) continue;
                 int part = -1, row = -1;
-                for (int j = 0; j < K; j++)
-                    if (plan.inputs[static_cast<size_t>(j)] == f) part = j;
-                for (int r = 0; r < R; r++) {
-                    if (plan.checked[static_cast<size_t>(r)] == f) part = K + r;
-                    if (row < 0 && plan.checked[static_cast<size_t>(r)] == k + __builtin_ctz(sig[static_cast<size_t>(f)])) row = r;
+                for (int j = 0; j < plan.K; j++)
+                    if (inputs[j] == f) part = j;
+                for (int r = 0; r < plan.R; r++) {
+                    if (checked[r] == f) part = plan.K + r;
+                    if (row < 0 && checked[r] == k + __builtin_ctz(sig[f])) row = r;
                 }
                 tab[f] = part < 0 || row < 0 ? 0xffffffffu : static_cast<uint32_t>(part) | static_cast<uint32_t>(row) << 8 | 1u << 16;
             }
         }
-        const void* d = nullptr;  // once per code, before anything is enqueued
-        if (const int rc = upload_table("correction table", tab, sizeof(tab), &d)) return rc;
-        slot = static_cast<const uint32_t*>(d);
-    }
-    out.dev = slot;
+        bytes.resize(sizeof(tab));
+        std::memcpy(bytes.data(), tab, sizeof(tab));
+        return 0;
+    }, &d);
+    out.dev = static_cast<const uint32_t*>(d);
     out.pairs = false;
-    return 0;
+    return rc;
 }
 
-// ecamd_xor_check (locate false) and ecamd_xor_locate: the parity bitmaps as a 0 / 1 map over GF(2^16).
-int xor_call(bool locate, int k, int m, int hd, const void* base, int64_t stripe_stride, int64_t frag_stride,
-             int64_t blocksize, int nstripes, uint32_t* d_status, uint32_t* d_suspects, void* stream,
-             void* fix_base = nullptr, uint32_t* d_counts = nullptr)
+// What every entry point runs, in this order: the device, the family's own test of the code (valid), the
+// layout, the family's plan (build, which also names the fragments the call covers), the caller's word
+// of those -- for an empty batch too --, the stages.
+template <class Valid, class Build>
+int check_entry(CheckCall c, uint32_t* covered, Valid&& valid, Build&& build)
 {
-    int dev = 0;
-    int rc = dev_ensure(&dev);
-    if (rc) return rc;
-    unsigned pb[32], db[32];
-    if (k <= 0 || m <= 0 || k + m > 32 || ecamd_xor_code_tables(k, m, hd, pb, db) != 0)
-        return dev_fail(ECAMD_EINVAL, "not a flat_xor_hd code: k=%d m=%d hd=%d", k, m, hd);
-    if ((rc = check_layout(locate, base, stripe_stride, frag_stride, blocksize, nstripes, d_status, d_suspects))) return rc;
+    int rc = dev_ensure(&c.dev);
+    if (rc || (rc = valid()) || (rc = check_layout(c))) return rc;
     CheckPlan p;
-    p.masks.assign(pb, pb + m);
-    p.sig.resize(static_cast<size_t>(k + m));
-    if (ecamd_xor_check_plan(k, m, hd, p.sig.data()) != 0) return dev_fail(ECAMD_EINVAL, "no check plan: k=%d m=%d hd=%d", k, m, hd);
-    for (int j = 0; j < k; j++) p.inputs.push_back(j);
-    for (int r = 0; r < m; r++) {
-        p.checked.push_back(k + r);
-        for (int j = 0; j < k; j++) p.bitmaps.push_back((pb[r] >> j) & 1u);
-    }
-    p.A = &p.bitmaps;
-    if (fix_base && (rc = xor_correct_table(dev, k, m, hd, 0u, p.sig, p, p.correct))) return rc;
-    return run_check(dev, p, base, stripe_stride, frag_stride, blocksize, nstripes, d_status, locate ? d_suspects : nullptr,
-                     stream, nullptr, fix_base, d_counts);
+    uint32_t mask = 0;
+    if ((rc = build(c, p, mask))) return rc;
+    if (covered) *covered = mask;
+    return run_check(c, p);
 }
 
-// ecamd_xor_check_degraded (locate false), ecamd_xor_locate_degraded and ecamd_xor_correct_degraded: the
-// rows of ecamd_xor_check_plan_degraded as a check plan.  The owner parity of each surviving row is
-// checked, every other participant -- the parities of retired pivot rows among them -- is an input, and
-// the map is the reduced rows over those inputs; a fragment that is lost, or that no surviving row
-// contains, is in neither list, so no stage reads or writes its slot.
-int xor_degraded_call(bool locate, int k, int m, int hd, const int* missing, const void* base, int64_t stripe_stride,
-                      int64_t frag_stride, int64_t blocksize, int nstripes, uint32_t* d_status, uint32_t* d_suspects,
-                      uint32_t* covered, void* stream, void* fix_base = nullptr, uint32_t* d_counts = nullptr)
+// rs_vand: the cached check map with the tables the call's stages ask for.  A bad layout is reported
+// before too many missing fragments: check_entry checks it before the plan is made.
+int rs_call(int k, int m, const int* missing, uint32_t* checked, const CheckCall& call)
 {
-    int dev = 0;
-    int rc = dev_ensure(&dev);
-    if (rc) return rc;
-    unsigned rows[32], sig[32], cov = 0;
-    if (k <= 0 || m <= 0 || k + m > 32 || ecamd_xor_check_plan_degraded(k, m, hd, missing, rows, sig, &cov) < 0)
-        return dev_fail(ECAMD_EINVAL, "not a flat_xor_hd code (k=%d m=%d hd=%d) or a bad list of missing fragments", k, m, hd);
-    if ((rc = check_layout(locate, base, stripe_stride, frag_stride, blocksize, nstripes, d_status, d_suspects))) return rc;
-    uint32_t lost = 0;
-    if (missing)
-        for (int i = 0; missing[i] > -1; i++) lost |= 1u << missing[i];
-    CheckPlan p;
-    p.degraded = true;
-    for (int r = 0; r < m; r++)
-        if (rows[r]) p.checked.push_back(k + r);
-    for (int f = 0; f < k + m; f++) {
-        if (!sig[f]) continue;
-        p.slots.frag.push_back(f);
-        if (!(f >= k && rows[f - k])) p.inputs.push_back(f);
-    }
-    const int K = static_cast<int>(p.inputs.size()), N = static_cast<int>(p.slots.frag.size());
-    for (int f : p.checked) {
-        const unsigned row = rows[f - k];
-        uint32_t over_inputs = 0, over_slots = 0;
-        for (int j = 0; j < K; j++) {
-            const unsigned bit = (row >> p.inputs[static_cast<size_t>(j)]) & 1u;
-            over_inputs |= bit << j;
-            p.bitmaps.push_back(static_cast<int>(bit));
+    auto valid = [&] {
+        if (k <= 0 || m < 0 || k + m > 32)
+            return dev_fail(ECAMD_EINVAL, "%s needs k + m <= 32 (k=%d m=%d)", call.locates ? "locate" : "check", k, m);
+        return 0;
+    };
+    return check_entry(call, checked, valid, [&](const CheckCall& c, CheckPlan& p, uint32_t& mask) {
+        int rc = check_map(k, m, missing, p.cached);
+        if (rc) return rc;
+        if (c.pairs_asked && (rc = check_map_pairs(p.cached, p.pairs))) return rc;
+        if (c.corrects && (rc = check_map_correct(p.cached, p.correct))) return rc;
+        for (int f : *p.cached.inputs) p.input(f);
+        for (int f : *p.cached.checked) {
+            p.checked(f);
+            mask |= 1u << f;
         }
-        for (int i = 0; i < N; i++) over_slots |= ((row >> p.slots.frag[static_cast<size_t>(i)]) & 1u) << i;
-        p.masks.push_back(over_inputs);
-        p.slots.masks.push_back(over_slots);
-        p.slots.row_bit.push_back(f);
-    }
-    for (int i = 0; i < N; i++) {
-        const unsigned over_owners = sig[p.slots.frag[static_cast<size_t>(i)]];
-        uint32_t packed = 0;  // the same over the surviving rows in their packed order
-        for (size_t r = 0; r < p.checked.size(); r++) packed |= ((over_owners >> (p.checked[r] - k)) & 1u) << r;
-        p.slots.sig.push_back(packed);
-    }
-    p.A = &p.bitmaps;
-    if (fix_base && !p.checked.empty() &&
-        (rc = xor_correct_table(dev, k, m, hd, lost, std::vector<uint32_t>(sig, sig + k + m), p, p.correct)))
-        return rc;
-    if (covered) *covered = cov;  // for an empty batch too
-    return run_check(dev, p, base, stripe_stride, frag_stride, blocksize, nstripes, d_status, locate ? d_suspects : nullptr,
-                     stream, nullptr, fix_base, d_counts);
+        p.A = p.cached.coeff;
+        p.fused = p.cached.map ? Fused::kRsBitsliced : Fused::kNone;
+        return 0;
+    });
+}
+
+// Flat XOR, full stripes: the parity bitmaps as a 0 / 1 map over GF(2^16).
+int xor_call(int k, int m, int hd, const CheckCall& call)
+{
+    unsigned pb[32], db[32];
+    auto valid = [&] {
+        if (k <= 0 || m <= 0 || k + m > 32 || ecamd_xor_code_tables(k, m, hd, pb, db) != 0)
+            return dev_fail(ECAMD_EINVAL, "not a flat_xor_hd code: k=%d m=%d hd=%d", k, m, hd);
+        return 0;
+    };
+    return check_entry(call, nullptr, valid, [&](const CheckCall& c, CheckPlan& p, uint32_t&) {
+        p.sig.resize(static_cast<size_t>(k + m));
+        if (ecamd_xor_check_plan(k, m, hd, p.sig.data()) != 0) return dev_fail(ECAMD_EINVAL, "no check plan: k=%d m=%d hd=%d", k, m, hd);
+        for (int j = 0; j < k; j++) p.input(j);
+        for (int r = 0; r < m; r++) {
+            p.checked(k + r);
+            for (int j = 0; j < k; j++) p.bitmaps.push_back((pb[r] >> j) & 1u);
+        }
+        p.A = &p.bitmaps;
+        p.fused = Fused::kXorFull;
+        return c.corrects ? xor_correct_table(c.dev, k, m, hd, 0u, p.sig.data(), p, p.correct) : 0;
+    });
+}
+
+// Flat XOR with fragments missing: the rows of ecamd_xor_check_plan_degraded as a check plan.  The owner
+// parity of each surviving row is checked, every other participant -- the parities of retired pivot rows
+// among them -- is an input, and the map is the reduced rows over those inputs; a fragment that is lost,
+// or that no surviving row contains, is in neither list, so no stage reads or writes its slot.  The plan
+// is validated before the layout.
+int xor_degraded_call(int k, int m, int hd, const int* missing, uint32_t* covered, const CheckCall& call)
+{
+    unsigned rows[32], sig[32], cov = 0;
+    auto valid = [&] {
+        if (k <= 0 || m <= 0 || k + m > 32 || ecamd_xor_check_plan_degraded(k, m, hd, missing, rows, sig, &cov) < 0)
+            return dev_fail(ECAMD_EINVAL, "not a flat_xor_hd code (k=%d m=%d hd=%d) or a bad list of missing fragments", k, m, hd);
+        return 0;
+    };
+    return check_entry(call, covered, valid, [&](const CheckCall& c, CheckPlan& p, uint32_t& mask) {
+        uint32_t lost = 0;
+        if (missing)
+            for (int i = 0; missing[i] > -1; i++) lost |= 1u << missing[i];
+        XorSlots& sl = p.slots;
+        for (int f = 0; f < k + m; f++) {
+            if (!sig[f]) continue;
+            sl.frag.push_back(f);
+            if (!(f >= k && rows[f - k])) p.input(f);
+        }
+        for (int r = 0; r < m; r++)
+            if (rows[r]) p.checked(k + r);
+        const uint8_t* checked = p.frag + p.K;
+        for (int r = 0; r < p.R; r++) {
+            const unsigned row = rows[checked[r] - k];
+            for (int j = 0; j < p.K; j++) p.bitmaps.push_back(static_cast<int>((row >> p.frag[j]) & 1u));
+            uint32_t over_slots = 0;
+            for (size_t i = 0; i < sl.frag.size(); i++) over_slots |= ((row >> sl.frag[i]) & 1u) << i;
+            sl.masks.push_back(over_slots);
+        }
+        for (int f : sl.frag) {
+            uint32_t packed = 0;  // sig[f], over the owners, over the surviving rows in their packed order
+            for (int r = 0; r < p.R; r++) packed |= ((sig[f] >> (checked[r] - k)) & 1u) << r;
+            sl.sig.push_back(packed);
+        }
+        p.A = &p.bitmaps;
+        p.fused = Fused::kXorSlots;
+        mask = cov;
+        return c.corrects && p.R > 0 ? xor_correct_table(c.dev, k, m, hd, lost, sig, p, p.correct) : 0;
+    });
 }
 
 // The host half of ecamd_rs_scrub, ecamd_xor_scrub and ecamd_rs_scrub_pairs, after the locate: a wait
-// for `stream`, the arrays read back, the counts, and -- when a stripe has exactly one suspect --
+// for the stream, the arrays read back, the counts, and -- when a stripe has exactly one suspect --
 // decode(lists) with lists[2*s..] = {f, -1} for such a stripe and {-1, -1} (the empty list) for every
-// other.  With d_pairs the lists are 3 long: {f, -1, -1}, {a, b, -1} for a stripe with a pair, and
+// other.  After a pair stage the lists are 3 long: {f, -1, -1}, {a, b, -1} for a stripe with a pair, and
 // the empty list.
+struct ScrubCounts {
+    int *clean, *repaired, *repaired_pairs, *unlocated;  // the caller's; any may be null
+};
 template <class Decode>
-int scrub_located(const uint32_t* d_status, const uint32_t* d_suspects, int nstripes, int* n_clean, int* n_repaired,
-                  int* n_unlocated, void* stream, Decode&& decode, const uint32_t* d_pairs = nullptr,
-                  int* n_repaired_pairs = nullptr)
+int scrub_located(const CheckCall& c, const ScrubCounts& out, Decode&& decode)
 {
+    const int nstripes = c.lay.nstripes;
     int clean = 0, repaired = 0, unlocated = 0, repaired_pairs = 0;
-    const size_t width = d_pairs ? 3 : 2;
+    const size_t width = c.pairs ? 3 : 2;
     if (nstripes > 0) {
-        HIP_TRY(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
+        HIP_TRY(hipStreamSynchronize(c.st()));
         std::vector<uint32_t> status(static_cast<size_t>(nstripes)), suspects(static_cast<size_t>(nstripes));
-        HIP_TRY(hipMemcpy(status.data(), d_status, status.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(suspects.data(), d_suspects, suspects.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(status.data(), c.status, status.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(suspects.data(), c.suspects, suspects.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
         std::vector<uint32_t> pairs;
-        if (d_pairs) {
+        if (c.pairs) {
             pairs.resize(static_cast<size_t>(nstripes));
-            HIP_TRY(hipMemcpy(pairs.data(), d_pairs, pairs.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(pairs.data(), c.pairs, pairs.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
         }
         std::vector<int> lists(static_cast<size_t>(nstripes) * width, -1);
         for (int s = 0; s < nstripes; s++) {
             const uint32_t sus = suspects[static_cast<size_t>(s)];
-            const uint32_t pr = d_pairs ? pairs[static_cast<size_t>(s)] : 0u;
+            const uint32_t pr = c.pairs ? pairs[static_cast<size_t>(s)] : 0u;
             if (!status[static_cast<size_t>(s)])
                 clean++;
             else if (sus && !(sus & (sus - 1))) {
@@ -1373,14 +1343,14 @@ int scrub_located(const uint32_t* d_status, const uint32_t* d_suspects, int nstr
                 unlocated++;
         }
         if (repaired || repaired_pairs) {
-            const int rc = decode(lists.data());
+            const int rc = decode(lists.data(), static_cast<int>(width));
             if (rc) return rc;
         }
     }
-    if (n_clean) *n_clean = clean;
-    if (n_repaired) *n_repaired = repaired;
-    if (n_unlocated) *n_unlocated = unlocated;
-    if (n_repaired_pairs) *n_repaired_pairs = repaired_pairs;
+    if (out.clean) *out.clean = clean;
+    if (out.repaired) *out.repaired = repaired;
+    if (out.unlocated) *out.unlocated = unlocated;
+    if (out.repaired_pairs) *out.repaired_pairs = repaired_pairs;
     return 0;
 }
 
@@ -1411,19 +1381,127 @@ void stripe_grid(int64_t units, int nstripes, int& chunks, int& slots)
 
 extern "C" {
 
+// ---- check ----
 int ecamd_rs_check(int k, int m, const int* missing, const void* base, int64_t stripe_stride, int64_t frag_stride,
                    int64_t blocksize, int nstripes, uint32_t* d_status, uint32_t* checked, void* stream)
 {
-    return rs_call(false, k, m, missing, base, stripe_stride, frag_stride, blocksize, nstripes, d_status, nullptr, checked,
-                   stream);
+    return rs_call(k, m, missing, checked, CheckCall(base, stripe_stride, frag_stride, blocksize, nstripes, d_status, stream));
 }
 
 int ecamd_xor_check(int k, int m, int hd, const void* base, int64_t stripe_stride, int64_t frag_stride,
                     int64_t blocksize, int nstripes, uint32_t* d_status, void* stream)
 {
-    return xor_call(false, k, m, hd, base, stripe_stride, frag_stride, blocksize, nstripes, d_status, nullptr, stream);
+    return xor_call(k, m, hd, CheckCall(base, stripe_stride, frag_stride, blocksize, nstripes, d_status, stream));
 }
 
+// ---- locate ----
+int ecamd_rs_locate(int k, int m, const int* missing, const void* base, int64_t stripe_stride, int64_t frag_stride,
+                    int64_t blocksize, int nstripes, uint32_t* d_status, uint32_t* d_suspects, uint32_t* checked,
+                    void* stream)
+{
+    return rs_call(k, m, missing, checked,
+                   CheckCall(base, stripe_stride, frag_stride, blocksize, nstripes, d_status, stream).locate(d_suspects));
+}
+
+int ecamd_xor_locate(int k, int m, int hd, const void* base, int64_t stripe_stride, int64_t frag_stride,
+                     int64_t blocksize, int nstripes, uint32_t* d_status, uint32_t* d_suspects, void* stream)
+{
+    return xor_call(k, m, hd, CheckCall(base, stripe_stride, frag_stride, blocksize, nstripes, d_status, stream).locate(d_suspects));
+}
+
+// ---- pairs ----
+int ecamd_rs_locate_pairs(int k, int m, const int* missing, const void* base, int64_t stripe_stride, int64_t frag_stride,
+                          int64_t blocksize, int nstripes, uint32_t* d_status, uint32_t* d_suspects, uint32_t* d_pairs,
+                          uint32_t* checked, void* stream)
+{
+    return rs_call(k, m, missing, checked,
+                   CheckCall(base, stripe_stride, frag_stride, blocksize, nstripes, d_status, stream).locate(d_suspects).pair(d_pairs));
+}
+
+// ---- correct ----
+// Locate, then correct in place on the same stream: no wait for the stream, no copy to the host, no
+// launch that depends on what the locate found -- correct_kernel reads the per-stripe words itself.
+int ecamd_rs_correct(int k, int m, const int* missing, void* base, int64_t stripe_stride, int64_t frag_stride,
+                     int64_t blocksize, int nstripes, uint32_t* d_status, uint32_t* d_suspects, uint32_t* d_pairs,
+                     uint32_t* d_counts, uint32_t* checked, void* stream)
+{
+    CheckCall c(base, stripe_stride, frag_stride, blocksize, nstripes, d_status, stream);
+    c.locate(d_suspects).correct(d_counts);
+    if (d_pairs) c.pair(d_pairs);  // without them: single fragments only
+    return rs_call(k, m, missing, checked, c);
+}
+
+int ecamd_xor_correct(int k, int m, int hd, void* base, int64_t stripe_stride, int64_t frag_stride, int64_t blocksize,
+                      int nstripes, uint32_t* d_status, uint32_t* d_suspects, uint32_t* d_counts, void* stream)
+{
+    return xor_call(k, m, hd,
+                    CheckCall(base, stripe_stride, frag_stride, blocksize, nstripes, d_status, stream).locate(d_suspects).correct(d_counts));
+}
+
+// ---- degraded: flat XOR with fragments missing ----
+int ecamd_xor_check_degraded(int k, int m, int hd, const int* missing, const void* base, int64_t stripe_stride,
+                             int64_t frag_stride, int64_t blocksize, int nstripes, uint32_t* d_status, uint32_t* covered,
+                             void* stream)
+{
+    return xor_degraded_call(k, m, hd, missing, covered,
+                             CheckCall(base, stripe_stride, frag_stride, blocksize, nstripes, d_status, stream));
+}
+
+int ecamd_xor_locate_degraded(int k, int m, int hd, const int* missing, const void* base, int64_t stripe_stride,
+                              int64_t frag_stride, int64_t blocksize, int nstripes, uint32_t* d_status, uint32_t* d_suspects,
+                              uint32_t* covered, void* stream)
+{
+    return xor_degraded_call(k, m, hd, missing, covered,
+                             CheckCall(base, stripe_stride, frag_stride, blocksize, nstripes, d_status, stream).locate(d_suspects));
+}
+
+int ecamd_xor_correct_degraded(int k, int m, int hd, const int* missing, void* base, int64_t stripe_stride,
+                               int64_t frag_stride, int64_t blocksize, int nstripes, uint32_t* d_status, uint32_t* d_suspects,
+                               uint32_t* d_counts, uint32_t* covered, void* stream)
+{
+    return xor_degraded_call(
+        k, m, hd, missing, covered,
+        CheckCall(base, stripe_stride, frag_stride, blocksize, nstripes, d_status, stream).locate(d_suspects).correct(d_counts));
+}
+
+// ---- scrub: a locate, a host wait, a decode of what it named ----
+int ecamd_rs_scrub(int k, int m, void* base, int64_t stripe_stride, int64_t frag_stride, int64_t blocksize,
+                   int nstripes, uint32_t* d_status, uint32_t* d_suspects, int* n_clean, int* n_repaired,
+                   int* n_unlocated, void* stream)
+{
+    if (m < 2) return dev_fail(ECAMD_EINVAL, "scrub needs m >= 2 to tell fragments apart (m=%d)", m);
+    const CheckCall c = CheckCall(base, stripe_stride, frag_stride, blocksize, nstripes, d_status, stream).locate(d_suspects);
+    if (const int rc = rs_call(k, m, nullptr, nullptr, c)) return rc;
+    return scrub_located(c, {n_clean, n_repaired, nullptr, n_unlocated}, [&](const int* lists, int width) {
+        return ecamd_rs_decode_multi(k, m, lists, width, 1, base, stripe_stride, frag_stride, blocksize, nstripes, stream);
+    });
+}
+
+int ecamd_rs_scrub_pairs(int k, int m, void* base, int64_t stripe_stride, int64_t frag_stride, int64_t blocksize,
+                         int nstripes, uint32_t* d_status, uint32_t* d_suspects, uint32_t* d_pairs, int* n_clean,
+                         int* n_repaired, int* n_repaired_pairs, int* n_unlocated, void* stream)
+{
+    if (m < 4) return dev_fail(ECAMD_EINVAL, "a pair repair needs m >= 4 (m=%d)", m);
+    const CheckCall c =
+        CheckCall(base, stripe_stride, frag_stride, blocksize, nstripes, d_status, stream).locate(d_suspects).pair(d_pairs);
+    if (const int rc = rs_call(k, m, nullptr, nullptr, c)) return rc;
+    return scrub_located(c, {n_clean, n_repaired, n_repaired_pairs, n_unlocated}, [&](const int* lists, int width) {
+        return ecamd_rs_decode_multi(k, m, lists, width, 1, base, stripe_stride, frag_stride, blocksize, nstripes, stream);
+    });
+}
+
+int ecamd_xor_scrub(int k, int m, int hd, void* base, int64_t stripe_stride, int64_t frag_stride, int64_t blocksize,
+                    int nstripes, uint32_t* d_status, uint32_t* d_suspects, int* n_clean, int* n_repaired,
+                    int* n_unlocated, void* stream)
+{
+    const CheckCall c = CheckCall(base, stripe_stride, frag_stride, blocksize, nstripes, d_status, stream).locate(d_suspects);
+    if (const int rc = xor_call(k, m, hd, c)) return rc;
+    return scrub_located(c, {n_clean, n_repaired, nullptr, n_unlocated}, [&](const int* lists, int width) {
+        return ecamd_xor_decode_multi(k, m, hd, lists, width, 1, base, stripe_stride, frag_stride, blocksize, nstripes, stream);
+    });
+}
+
+// ---- prebuild (build time, no GPU): the code objects the fused rs_vand stage will ask for ----
 int ecamd_check_prebuild(int k, int m, const int* missing, const char* arch, const char* dir)
 {
     FragmentMap fm;
@@ -1440,116 +1518,6 @@ int ecamd_check_prebuild(int k, int m, const int* missing, const char* arch, con
     return built;
 }
 
-int ecamd_rs_locate(int k, int m, const int* missing, const void* base, int64_t stripe_stride, int64_t frag_stride,
-                    int64_t blocksize, int nstripes, uint32_t* d_status, uint32_t* d_suspects, uint32_t* checked,
-                    void* stream)
-{
-    return rs_call(true, k, m, missing, base, stripe_stride, frag_stride, blocksize, nstripes, d_status, d_suspects, checked,
-                   stream);
-}
-
-int ecamd_xor_locate(int k, int m, int hd, const void* base, int64_t stripe_stride, int64_t frag_stride,
-                     int64_t blocksize, int nstripes, uint32_t* d_status, uint32_t* d_suspects, void* stream)
-{
-    return xor_call(true, k, m, hd, base, stripe_stride, frag_stride, blocksize, nstripes, d_status, d_suspects, stream);
-}
-
-int ecamd_rs_scrub(int k, int m, void* base, int64_t stripe_stride, int64_t frag_stride, int64_t blocksize,
-                   int nstripes, uint32_t* d_status, uint32_t* d_suspects, int* n_clean, int* n_repaired,
-                   int* n_unlocated, void* stream)
-{
-    if (m < 2) return dev_fail(ECAMD_EINVAL, "scrub needs m >= 2 to tell fragments apart (m=%d)", m);
-    int rc = ecamd_rs_locate(k, m, nullptr, base, stripe_stride, frag_stride, blocksize, nstripes, d_status, d_suspects,
-                             nullptr, stream);
-    if (rc) return rc;
-    return scrub_located(d_status, d_suspects, nstripes, n_clean, n_repaired, n_unlocated, stream, [&](const int* lists) {
-        return ecamd_rs_decode_multi(k, m, lists, 2, 1, base, stripe_stride, frag_stride, blocksize, nstripes, stream);
-    });
-}
-
-int ecamd_rs_locate_pairs(int k, int m, const int* missing, const void* base, int64_t stripe_stride, int64_t frag_stride,
-                          int64_t blocksize, int nstripes, uint32_t* d_status, uint32_t* d_suspects, uint32_t* d_pairs,
-                          uint32_t* checked, void* stream)
-{
-    return rs_call(true, k, m, missing, base, stripe_stride, frag_stride, blocksize, nstripes, d_status, d_suspects, checked,
-                   stream, true, d_pairs);
-}
-
-int ecamd_rs_scrub_pairs(int k, int m, void* base, int64_t stripe_stride, int64_t frag_stride, int64_t blocksize,
-                         int nstripes, uint32_t* d_status, uint32_t* d_suspects, uint32_t* d_pairs, int* n_clean,
-                         int* n_repaired, int* n_repaired_pairs, int* n_unlocated, void* stream)
-{
-    if (m < 4) return dev_fail(ECAMD_EINVAL, "a pair repair needs m >= 4 (m=%d)", m);
-    int rc = ecamd_rs_locate_pairs(k, m, nullptr, base, stripe_stride, frag_stride, blocksize, nstripes, d_status, d_suspects,
-                                   d_pairs, nullptr, stream);
-    if (rc) return rc;
-    return scrub_located(
-        d_status, d_suspects, nstripes, n_clean, n_repaired, n_unlocated, stream,
-        [&](const int* lists) {
-            return ecamd_rs_decode_multi(k, m, lists, 3, 1, base, stripe_stride, frag_stride, blocksize, nstripes, stream);
-        },
-        d_pairs, n_repaired_pairs);
-}
-
-long long ecamd_locate_pairs_launches(void) { return g_pairs_launches.load(std::memory_order_relaxed); }
-
-int ecamd_xor_scrub(int k, int m, int hd, void* base, int64_t stripe_stride, int64_t frag_stride, int64_t blocksize,
-                    int nstripes, uint32_t* d_status, uint32_t* d_suspects, int* n_clean, int* n_repaired,
-                    int* n_unlocated, void* stream)
-{
-    int rc = ecamd_xor_locate(k, m, hd, base, stripe_stride, frag_stride, blocksize, nstripes, d_status, d_suspects, stream);
-    if (rc) return rc;
-    return scrub_located(d_status, d_suspects, nstripes, n_clean, n_repaired, n_unlocated, stream, [&](const int* lists) {
-        return ecamd_xor_decode_multi(k, m, hd, lists, 2, 1, base, stripe_stride, frag_stride, blocksize, nstripes, stream);
-    });
-}
-
-// Locate, then correct in place on the same stream: no wait for the stream, no copy to the host, no
-// launch that depends on what the locate found -- correct_kernel reads the per-stripe words itself.
-int ecamd_rs_correct(int k, int m, const int* missing, void* base, int64_t stripe_stride, int64_t frag_stride,
-                     int64_t blocksize, int nstripes, uint32_t* d_status, uint32_t* d_suspects, uint32_t* d_pairs,
-                     uint32_t* d_counts, uint32_t* checked, void* stream)
-{
-    return rs_call(true, k, m, missing, base, stripe_stride, frag_stride, blocksize, nstripes, d_status, d_suspects, checked,
-                   stream, d_pairs != nullptr, d_pairs, base, d_counts);
-}
-
-int ecamd_xor_correct(int k, int m, int hd, void* base, int64_t stripe_stride, int64_t frag_stride, int64_t blocksize,
-                      int nstripes, uint32_t* d_status, uint32_t* d_suspects, uint32_t* d_counts, void* stream)
-{
-    return xor_call(true, k, m, hd, base, stripe_stride, frag_stride, blocksize, nstripes, d_status, d_suspects, stream, base,
-                    d_counts);
-}
-
-int ecamd_xor_check_degraded(int k, int m, int hd, const int* missing, const void* base, int64_t stripe_stride,
-                             int64_t frag_stride, int64_t blocksize, int nstripes, uint32_t* d_status, uint32_t* covered,
-                             void* stream)
-{
-    return xor_degraded_call(false, k, m, hd, missing, base, stripe_stride, frag_stride, blocksize, nstripes, d_status, nullptr,
-                             covered, stream);
-}
-
-int ecamd_xor_locate_degraded(int k, int m, int hd, const int* missing, const void* base, int64_t stripe_stride,
-                              int64_t frag_stride, int64_t blocksize, int nstripes, uint32_t* d_status, uint32_t* d_suspects,
-                              uint32_t* covered, void* stream)
-{
-    return xor_degraded_call(true, k, m, hd, missing, base, stripe_stride, frag_stride, blocksize, nstripes, d_status,
-                             d_suspects, covered, stream);
-}
-
-int ecamd_xor_correct_degraded(int k, int m, int hd, const int* missing, void* base, int64_t stripe_stride,
-                               int64_t frag_stride, int64_t blocksize, int nstripes, uint32_t* d_status, uint32_t* d_suspects,
-                               uint32_t* d_counts, uint32_t* covered, void* stream)
-{
-    return xor_degraded_call(true, k, m, hd, missing, base, stripe_stride, frag_stride, blocksize, nstripes, d_status,
-                             d_suspects, covered, stream, base, d_counts);
-}
-
-long long ecamd_correct_launches(void) { return g_correct_launches.load(std::memory_order_relaxed); }
-
-long long ecamd_xor_check_fused_launches(void) { return g_xor_check_fused.load(std::memory_order_relaxed); }
-long long ecamd_xor_locate_fused_launches(void) { return g_xor_locate_fused.load(std::memory_order_relaxed); }
-
 int ecamd_locate_prebuild(int k, int m, const int* missing, const char* arch, const char* dir)
 {
     FragmentMap fm;
@@ -1562,5 +1530,11 @@ int ecamd_locate_prebuild(int k, int m, const int* missing, const char* arch, co
     if (r < 0) return dev_fail(ECAMD_EHIP, "locate prebuild failed (%d) for a %dx%d map", r, R, K + R);
     return r;
 }
+
+// ---- counters: launches enqueued by this process ----
+long long ecamd_xor_check_fused_launches(void) { return g_xor_check_fused.load(std::memory_order_relaxed); }
+long long ecamd_xor_locate_fused_launches(void) { return g_xor_locate_fused.load(std::memory_order_relaxed); }
+long long ecamd_locate_pairs_launches(void) { return g_pairs_launches.load(std::memory_order_relaxed); }
+long long ecamd_correct_launches(void) { return g_correct_launches.load(std::memory_order_relaxed); }
 
 }  // extern "C"

@@ -14,10 +14,8 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <array>
 #include <atomic>
-#include <map>
-#include <mutex>
+#include <cstring>
 #include <vector>
 
 #include "../host/gf16.hpp"
@@ -206,36 +204,18 @@ std::atomic<long long> g_decode_masks_launches{0};
 // (device, k, m), and kept for the life of the process (at most 1536 bytes each).
 int masks_generator(int dev, int k, int m, const uint16_t** out)
 {
-    static std::mutex mu;
-    static std::map<std::array<int, 3>, const uint16_t*> gens;
-    const std::lock_guard<std::mutex> lk(mu);
-    const uint16_t*& slot = gens[{dev, k, m}];
-    if (!slot) {
+    static CodeTables<3> gens("generator upload");
+    const void* d = nullptr;
+    const int rc = gens.get({dev, k, m}, [&](std::vector<uint8_t>& bytes) {
         const std::vector<int> G = rs_generator(k, m);
         if (G.empty()) return dev_fail(ECAMD_EINVAL, "no generator for k=%d m=%d", k, m);
         const std::vector<uint16_t> g16(G.begin(), G.end());
-        const void* d = nullptr;  // once per code
-        if (const int rc = upload_table("generator upload", g16.data(), g16.size() * sizeof(uint16_t), &d)) return rc;
-        slot = static_cast<const uint16_t*>(d);
-    }
-    *out = slot;
-    return 0;
-}
-
-template <int W>
-void masks_launch(int groups, dim3 grid, size_t lds, hipStream_t st, const MasksArgs& a)
-{
-    const dim3 block(256);
-    switch (groups) {  // k <= 32
-    case 1: hipLaunchKernelGGL((decode_masks_kernel<W, 1>), grid, block, lds, st, a); break;
-    case 2: hipLaunchKernelGGL((decode_masks_kernel<W, 2>), grid, block, lds, st, a); break;
-    case 3: hipLaunchKernelGGL((decode_masks_kernel<W, 3>), grid, block, lds, st, a); break;
-    case 4: hipLaunchKernelGGL((decode_masks_kernel<W, 4>), grid, block, lds, st, a); break;
-    case 5: hipLaunchKernelGGL((decode_masks_kernel<W, 5>), grid, block, lds, st, a); break;
-    case 6: hipLaunchKernelGGL((decode_masks_kernel<W, 6>), grid, block, lds, st, a); break;
-    case 7: hipLaunchKernelGGL((decode_masks_kernel<W, 7>), grid, block, lds, st, a); break;
-    default: hipLaunchKernelGGL((decode_masks_kernel<W, 8>), grid, block, lds, st, a); break;
-    }
+        bytes.resize(g16.size() * sizeof(uint16_t));
+        std::memcpy(bytes.data(), g16.data(), bytes.size());
+        return 0;
+    }, &d);
+    *out = static_cast<const uint16_t*>(d);
+    return rc;
 }
 
 }  // namespace
@@ -251,10 +231,9 @@ int ecamd_rs_decode_masks(int k, int m, const uint32_t* d_lost, int rebuild_pari
     if (rc) return rc;
     if (k <= 0 || m < 0 || k + m > kMasksMaxFrags || m > kMasksMaxOut)
         return dev_fail(ECAMD_EINVAL, "decode_masks needs k + m <= 32 and m <= 8 (k=%d m=%d)", k, m);
-    if (!d_lost || !base || nstripes < 0 || blocksize < 1 || frag_stride < blocksize)
-        return dev_fail(ECAMD_EINVAL, "bad masks / base / blocksize / strides");
-    if ((reinterpret_cast<uintptr_t>(base) & 15u) || stripe_stride % 16 || frag_stride % 16)
-        return dev_fail(ECAMD_EINVAL, "fragment addresses must be 16-byte aligned");
+    const StripeLayout lay{static_cast<uint8_t*>(base), stripe_stride, frag_stride, blocksize, nstripes};
+    if (!d_lost || !lay.sane()) return dev_fail(ECAMD_EINVAL, "bad masks / base / blocksize / strides");
+    if (!lay.aligned16()) return dev_fail(ECAMD_EINVAL, "fragment addresses must be 16-byte aligned");
     // an odd size ends in half a word; ecamd_rs_locate and ecamd_rs_correct refuse it as well
     if (blocksize & 1) return dev_fail(ECAMD_EINVAL, "decode_masks needs an even blocksize (%lld)", static_cast<long long>(blocksize));
     if (nstripes == 0) return 0;
@@ -270,7 +249,7 @@ int ecamd_rs_decode_masks(int k, int m, const uint32_t* d_lost, int rebuild_pari
                        rebuild_parity ? 1 : 0, recs, d_result);
     HIP_TRY(hipGetLastError());
     MasksArgs a{};
-    a.base = static_cast<uint8_t*>(base);
+    a.base = lay.base;
     a.recs = recs;
     a.stripe_stride = stripe_stride;
     a.frag_stride = frag_stride;
@@ -280,14 +259,19 @@ int ecamd_rs_decode_masks(int k, int m, const uint32_t* d_lost, int rebuild_pari
     int cols = 0, slots = 0;  // a tile column per 16 tiles of 4096 bytes (stripe_grid's units: 16-byte chunks)
     stripe_grid((blocksize + 15) >> 4, nstripes, cols, slots);
     const dim3 grid(static_cast<unsigned>(cols), static_cast<unsigned>(slots));
-    const int groups = (k + 3) / 4, W = m <= 2 ? 2 : m <= 4 ? 4 : 8;
+    const int W = m <= 2 ? 2 : m <= 4 ? 4 : 8;
     const size_t lds = static_cast<size_t>(k) * 64 * 2 * W;
+    auto launch = [&](auto w) {
+        with_groups<1, 8>((k + 3) / 4, [&](auto g) {  // k <= 32
+            hipLaunchKernelGGL((decode_masks_kernel<decltype(w)::value, decltype(g)::value>), grid, dim3(256), lds, st, a);
+        });
+    };
     if (W == 2)
-        masks_launch<2>(groups, grid, lds, st, a);
+        launch(std::integral_constant<int, 2>{});
     else if (W == 4)
-        masks_launch<4>(groups, grid, lds, st, a);
+        launch(std::integral_constant<int, 4>{});
     else
-        masks_launch<8>(groups, grid, lds, st, a);
+        launch(std::integral_constant<int, 8>{});
     HIP_TRY(hipGetLastError());
     g_decode_masks_launches.fetch_add(1, std::memory_order_relaxed);
     if (d_counts) {

@@ -685,27 +685,29 @@ int64_t launch_bitslice(const ecamd_map* map, int row0, int nrows, const ApplyAr
     return *rc ? 0 : cover;
 }
 
-int64_t check_fused(int dev, const std::vector<int>& A, int K, int row0, int nrows, const uint8_t* base,
-                    int64_t stripe_stride, const int64_t* in_off, const int64_t* chk_off, const uint8_t* bits,
-                    uint32_t* d_status, uint32_t* d_suspects, const uint8_t* in_bits, int64_t blocksize, int nstripes,
-                    void* stream)
+int64_t check_fused(int dev, const std::vector<int>& A, const Participants& p, int row0, int nrows, const StripeLayout& lay,
+                    uint32_t* d_status, uint32_t* d_suspects, void* stream)
 {
+    const int K = p.K;
     if (nrows > kBsMaxR || K + nrows > kBsMaxK) return 0;
     ecamd_map syn;
     syn.device = dev;
     syn.R = nrows;
     syn.K = K + nrows;
     syn.coeff = syndrome_rows(A, K, row0, nrows);
-    std::vector<int64_t> off(in_off, in_off + K);
-    off.insert(off.end(), chk_off + row0, chk_off + row0 + nrows);
-    std::vector<uint8_t> frag_bits(in_bits, in_bits + K);  // of the map's inputs: the K inputs, then the checked rows
-    frag_bits.insert(frag_bits.end(), bits + row0, bits + row0 + nrows);
+    // the map's inputs: the K inputs, then the checked rows of this group
+    const int64_t* chk_off = p.off + K + row0;
+    const uint8_t* chk_bit = p.bit + K + row0;
+    std::vector<int64_t> off(p.off, p.off + K);
+    off.insert(off.end(), chk_off, chk_off + nrows);
+    std::vector<uint8_t> frag_bits(p.bit, p.bit + K);
+    frag_bits.insert(frag_bits.end(), chk_bit, chk_bit + nrows);
     ApplyArgs a{};
-    a.in_base = base;
-    a.in_stride = stripe_stride;
-    const BsCheck chk{d_status, bits + row0, d_suspects, frag_bits.data()};
+    a.in_base = lay.base;
+    a.in_stride = lay.stripe_stride;
+    const BsCheck chk{d_status, chk_bit, d_suspects, frag_bits.data()};
     int rc = 0;
-    const int64_t cover = launch_bitslice(&syn, 0, nrows, a, off.data(), nullptr, blocksize, nstripes,
+    const int64_t cover = launch_bitslice(&syn, 0, nrows, a, off.data(), nullptr, lay.blocksize, lay.nstripes,
                                           static_cast<hipStream_t>(stream), &rc, nullptr, &chk);
     return rc ? rc : cover;
 }

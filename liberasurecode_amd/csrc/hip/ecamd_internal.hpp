@@ -5,8 +5,11 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <array>
+#include <map>
 #include <memory>
 #include <mutex>
+#include <type_traits>
 
 struct ecamd_map;
 
@@ -52,6 +55,57 @@ inline bool frags_aligned16(const void* in_base, const void* out_base, int64_t i
     for (int r = 0; r < R; r++) ok = ok && (out_off[r] % 16) == 0;
     return ok;
 }
+
+// Where a strided batch lies: fragment f of stripe s at base + s*stripe_stride + f*frag_stride, blocksize
+// bytes each.  The two rules every entry point over such a batch starts with; the message, and the
+// null tests of its other pointers, are the entry point's own.
+struct StripeLayout {
+    uint8_t* base;  // written only by the calls that say so (correct, decode_masks)
+    int64_t stripe_stride, frag_stride, blocksize;
+    int nstripes;
+    bool sane() const { return base && nstripes >= 0 && blocksize >= 1 && frag_stride >= blocksize; }
+    bool aligned16() const { return frags_aligned16(base, base, stripe_stride, stripe_stride, &frag_stride, 1, nullptr, 0); }
+};
+
+// f(std::integral_constant<int, N>{}) with N = groups held to [Lo, Hi]: the one place a count of
+// four-fragment load groups picks the kernel<N> to launch.
+template <int Lo, int Hi, class F>
+void with_groups(int groups, F&& f)
+{
+    if constexpr (Lo < Hi) {
+        if (groups > Lo) return with_groups<Lo + 1, Hi>(groups, f);
+    }
+    f(std::integral_constant<int, Lo>{});
+}
+
+// The device tables of one kind, one per code: made at the first call that asks for `key` -- (device,
+// code...) --, by build(bytes) (0, or its own dev_fail) and upload_table(what), and kept for the life of
+// the process.  A table that could not be made is tried again by the next call.
+template <size_t N>
+class CodeTables {
+public:
+    explicit CodeTables(const char* what) : what_(what) {}
+    template <class Build>
+    int get(const std::array<int, N>& key, Build&& build, const void** out)
+    {
+        const std::lock_guard<std::mutex> lk(mu_);
+        const void*& slot = tables_[key];
+        if (!slot) {
+            std::vector<uint8_t> bytes;
+            if (const int rc = build(bytes)) return rc;
+            const void* d = nullptr;  // once per code, before anything of the call is enqueued
+            if (const int rc = upload_table(what_, bytes.data(), bytes.size(), &d)) return rc;
+            slot = d;
+        }
+        *out = slot;
+        return 0;
+    }
+
+private:
+    const char* what_;
+    std::mutex mu_;
+    std::map<std::array<int, N>, const void*> tables_;
+};
 
 // Asynchronous upload of a small host table (stripe list, pointer table) on `stream` through a
 // ring of pinned slots per (device, stream); call end() after enqueuing the launches that read
@@ -150,17 +204,24 @@ int check_map(int k, int m, const int* missing, CheckMap& out);
 // the grid within 4096 workgroups; knob pairs_grid > 0 caps both dimensions.
 void stripe_grid(int64_t units, int nstripes, int& chunks, int& slots);
 
+// ---- ecamd_check.hip: who takes part in a check, locate or correct call ----
+// The K inputs, then the R checked rows (K + R <= 32): participant c of stripe s lies at base +
+// s*stripe_stride + off[c] and is fragment bit[c]; mask has the bits of them all.
+struct Participants {
+    int K = 0, R = 0;
+    int64_t off[32] = {};
+    uint8_t bit[32] = {};
+    uint32_t mask = 0;
+};
+
 // ---- ecamd_device.hip ----
 // Fused stage of a check or, with d_suspects, of a locate: rows [row0, row0 + nrows) of the R x K
 // matrix A as the syndrome map [A | I] through the check / locate form of the bitsliced kernel, over
-// whole tiles of every stripe.  Input j of stripe s at base + s*stripe_stride + in_off[j], fragment
-// index in_bits[j]; checked row r at chk_off[r], fragment index bits[r] (both arrays of all R rows).
+// whole tiles of every stripe of `lay`, the inputs and checked rows where `p` has them.
 // Returns the bytes of each fragment covered -- 0 when the shape, the knobs or a kernel still
 // compiling decline, nothing launched -- or an error (< 0).
-int64_t check_fused(int dev, const std::vector<int>& A, int K, int row0, int nrows, const uint8_t* base,
-                    int64_t stripe_stride, const int64_t* in_off, const int64_t* chk_off, const uint8_t* bits,
-                    uint32_t* d_status, uint32_t* d_suspects, const uint8_t* in_bits, int64_t blocksize, int nstripes,
-                    void* stream);
+int64_t check_fused(int dev, const std::vector<int>& A, const Participants& p, int row0, int nrows, const StripeLayout& lay,
+                    uint32_t* d_status, uint32_t* d_suspects, void* stream);
 // Build time (no GPU): the code object check_fused will ask for over the same rows, into `dir`
 // (bitslice_prebuild's result: 1 present, 0 no fused form under the current knobs, < 0 failed; -6
 // from the locate form: every build needs scratch, so the run time declines it too).

@@ -13,10 +13,7 @@
 // T, the data kernel's tile, is 4096 bytes: 256 lanes of one 16-byte chunk per fragment.
 #include <hip/hip_runtime.h>
 
-#include <array>
 #include <atomic>
-#include <map>
-#include <mutex>
 #include <vector>
 
 #include "ecamd.h"
@@ -233,21 +230,17 @@ std::atomic<long long> g_xor_decode_masks_launches{0};
 // init_xor_hd_code rejects.
 int xor_masks_table(int dev, int k, int m, int hd, const XorMasksEntry** out)
 {
-    static std::mutex mu;
-    static std::map<std::array<int, 4>, const XorMasksEntry*> tables;
-    const std::lock_guard<std::mutex> lk(mu);
-    const XorMasksEntry*& slot = tables[{dev, k, m, hd}];
-    if (!slot) {
-        std::vector<XorMasksEntry> tab(static_cast<size_t>(kXorMasksMaxEntries));
-        const int count = ecamd_xor_decode_masks_plan(k, m, hd, tab.data(), kXorMasksMaxEntries);
+    static CodeTables<4> tables("decode table upload");
+    const void* d = nullptr;
+    const int rc = tables.get({dev, k, m, hd}, [&](std::vector<uint8_t>& bytes) {
+        bytes.resize(static_cast<size_t>(kXorMasksMaxEntries) * sizeof(XorMasksEntry));
+        const int count = ecamd_xor_decode_masks_plan(k, m, hd, bytes.data(), kXorMasksMaxEntries);
         if (count < 1 || count > kXorMasksMaxEntries) return dev_fail(ECAMD_EINVAL, "no decode table for the flat XOR code (%d,%d,%d)", k, m, hd);
-        const void* d = nullptr;  // once per code
-        if (const int rc = upload_table("decode table upload", tab.data(), static_cast<size_t>(count) * sizeof(XorMasksEntry), &d))
-            return rc;
-        slot = static_cast<const XorMasksEntry*>(d);
-    }
-    *out = slot;
-    return 0;
+        bytes.resize(static_cast<size_t>(count) * sizeof(XorMasksEntry));
+        return 0;
+    }, &d);
+    *out = static_cast<const XorMasksEntry*>(d);
+    return rc;
 }
 
 }  // namespace
@@ -263,16 +256,15 @@ int ecamd_xor_decode_masks(int k, int m, int hd, const uint32_t* d_lost, int dec
     if (rc) return rc;
     if (k <= 0 || m <= 0 || k + m > 32 || ecamd_xor_code_tables(k, m, hd, nullptr, nullptr) != 0)
         return dev_fail(ECAMD_EINVAL, "(%d,%d,%d) is not a flat_xor_hd code", k, m, hd);
-    if (!d_lost || !base || nstripes < 0 || blocksize < 1 || frag_stride < blocksize)
-        return dev_fail(ECAMD_EINVAL, "bad masks / base / blocksize / strides");
-    if ((reinterpret_cast<uintptr_t>(base) & 15u) || stripe_stride % 16 || frag_stride % 16)
-        return dev_fail(ECAMD_EINVAL, "fragment addresses must be 16-byte aligned");
+    const StripeLayout lay{static_cast<uint8_t*>(base), stripe_stride, frag_stride, blocksize, nstripes};
+    if (!d_lost || !lay.sane()) return dev_fail(ECAMD_EINVAL, "bad masks / base / blocksize / strides");
+    if (!lay.aligned16()) return dev_fail(ECAMD_EINVAL, "fragment addresses must be 16-byte aligned");
     if (nstripes == 0) return 0;
     const XorMasksEntry* d_table = nullptr;
     if ((rc = xor_masks_table(dev, k, m, hd, &d_table))) return rc;
     const auto st = static_cast<hipStream_t>(stream);
     XorMasksArgs a{};
-    a.base = static_cast<uint8_t*>(base);
+    a.base = lay.base;
     a.lost = d_lost;
     a.table = d_table;
     a.result = d_result;
