@@ -667,11 +667,60 @@ int ecamd_frame_verify(int nfrag, int64_t blocksize, int legacy, const void *d_f
  *                                                                 or ecamd_xor_decode_masks(base = d_frags + 80)
  * heals payload damage of framed stripes on one stream with one wait at the end: the header still
  * holds the original payload's CRC32, so the rebuilt payload matches it again.  Fragments with a bad
- * HEADER (bits 0-3) are not covered: the decode rebuilds payloads only and no header is restamped, so
- * do not pass those bits unless the headers are rewritten by other means (ecamd_frame_reconstruct).
+ * HEADER (bits 0-3) -- a replaced disk, a slot of garbage -- need their header restamped as well: pass
+ * bits = 0x1F and give the masks to ecamd_frame_reconstruct_masks (below) instead of the payload decode.
  * ECAMD_EINVAL (nothing written) for null arrays, nfrag < 1 or > 32, nstripes < 0. */
 int ecamd_frame_status_masks(int nfrag, const uint32_t *d_frag_status, uint32_t bits, int nstripes,
                              uint32_t *d_masks, void *stream);
+/* ---- whole fragments from device masks: ecamd_frame_reconstruct for batches in which every stripe lost
+ * its own fragments, headers included ----
+ * backend 6 (rs_vand) or 3 (flat_xor_hd); checksum and obj_size as for ecamd_frame_reconstruct; the layout
+ * that of the other framed calls (blocksize from ecamd_frame_geometry).  d_lost (nstripes uint32, DEVICE
+ * memory) holds one mask per stripe, bit f set when fragment f of stripe s is lost, header and payload;
+ * the word is read on the device, in stream order, exactly as ecamd_rs_decode_masks reads it.  With
+ *   ecamd_frame_verify -> ecamd_frame_status_masks(bits = 0x1F) -> ecamd_frame_reconstruct_masks
+ * every kind of fragment damage the audit can see is healed on one stream with one wait at the end, and
+ * a second audit comes back all zero.  Per stripe, with L = d_lost[s]:
+ *   L == 0                          nothing of the stripe is read or written; d_result[s] = 0.
+ *   not recoverable                 by the payload decode's rule and by no other -- a bit >= k+m, more than
+ *                                   m bits (rs_vand), hd or more bits (flat_xor_hd): nothing of the stripe
+ *                                   is written, header or payload; d_result[s] = 0x80000000 | popcount(L).
+ *   otherwise                       every fragment f in L is rebuilt whole.  Its payload is what
+ *                                   ecamd_rs_decode_masks(rebuild_parity 1) / ecamd_xor_decode_masks(
+ *                                   decode_parity 1) writes at base = d_frags + 80; its header is what
+ *                                   ecamd_frame_reconstruct stamps for dest = f: add_fragment_metadata on a
+ *                                   zeroed header, the payload CRC32 stored when checksum == 2 (the machine
+ *                                   LIBERASURECODE_WRITE_LEGACY_CRC selects), any other checksum type
+ *                                   stored but not computed.  d_result[s] = popcount(L).  On a consistent
+ *                                   stripe the fragment is the one liberasurecode_encode produced, byte
+ *                                   for byte.
+ * Never written: surviving fragments (header or payload), the bytes between 80 + blocksize and frag_stride,
+ * anything in front of d_frags.  Never read: lost slots before they are rebuilt, and -- in the stamp stage --
+ * the payload of any fragment that was not rebuilt.
+ * d_result (nstripes uint32, device memory, may be NULL: library scratch then holds the words, which the
+ * stamp stage reads -- whether a stripe is recoverable stays the decode kernel's decision).  d_counts (3
+ * uint32, device memory, may be NULL): (left alone, rebuilt, unrecoverable) as ecamd_rs_decode_masks.
+ * There is no host dependence inside the call: no stream synchronise, no copy to the host, no launch whose
+ * shape depends on the masks, no map-cache entry, no compile, and no allocation beyond library scratch per
+ * (device, stream) that grows only when a larger batch arrives.  The launches are fixed: the payload
+ * decode's, then -- with checksum == 2 -- a masked CRC-partial kernel (one wave per (stripe, j, span), j <
+ * min(m, 8) or hd - 1: a wave reads the stripe's result and mask words as scalars, takes the j-th lost
+ * fragment and leaves on a scalar branch when there is none, so a stripe with nothing to stamp costs two
+ * word loads per wave and no payload traffic; the span arithmetic, image and knobs are crc_partial_kernel's),
+ * then one stamp kernel (one thread per (stripe, j): the fold of the span partials and tail bytes, the 80
+ * header bytes as five 16-byte stores).  Neither grid nor the partials scale with k + m.
+ * ECAMD_EINVAL, with everything untouched, for what the other framed calls reject (backend, code, 16-byte
+ * aligned base and strides, frag_stride >= 80 + blocksize rounded up to 16), a null d_lost or d_frags,
+ * nstripes < 0 and, for backend 6, m > 8 or k+m > 32 (ecamd_rs_decode_masks' limits).  nstripes == 0
+ * returns 0 and writes nothing.
+ * When to prefer ecamd_frame_reconstruct: DESIGN.md "Whole fragments from device masks", INTEGRATION.md. */
+int ecamd_frame_reconstruct_masks(int backend, int k, int m, int hd, int checksum, const uint32_t *d_lost,
+                                  void *d_frags, int64_t stripe_stride, int64_t frag_stride, uint64_t obj_size,
+                                  int nstripes, uint32_t *d_result /* may be NULL */,
+                                  uint32_t *d_counts /* 3 words, may be NULL */, void *stream);
+/* Launches of frame_stamp_masks_kernel (the stamp kernel) enqueued by this process: one per call with a
+ * non-empty batch. */
+long long ecamd_frame_reconstruct_masks_launches(void);
 /* zlib crc32(0, buf, len) (legacy = 0) or liberasurecode_crc32_alt(0, buf, len) (legacy = 1) of
  * every buffer d_base + s*stripe_stride + f*frag_stride, f < nfrag: d_crc[s*nfrag + f]. */
 int ecamd_crc32(int legacy, const void *d_base, int64_t stripe_stride, int64_t frag_stride,

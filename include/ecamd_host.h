@@ -173,6 +173,15 @@ int ecamd_xor_plan(int op, int k, int m, int hd, const unsigned int *parity_bms,
  * init_xor_hd_code rejects; -2, which no shipped code returns, if a plan does not have that form. */
 int ecamd_xor_decode_masks_plan(int k, int m, int hd, void *table, int capacity);
 
+/* The 80-byte fragment header the framed device calls stamp (ecamd_frame_encode, _reconstruct,
+ * _reconstruct_masks in ecamd.h), from the text the device kernels run (csrc/hip/ecamd_frame_header.hpp):
+ * add_fragment_metadata on a zeroed header for fragment idx of an object of obj_size bytes with payloads
+ * of blocksize bytes.  payload_crc is stored when checksum is 2 (CRC32); any other type is stored, not
+ * computed.  legacy != 0: the metadata checksum by liberasurecode_crc32_alt instead of zlib's crc32.
+ * Returns 0; -1 for a null out or idx < 0. */
+int ecamd_frame_header(int idx, uint32_t blocksize, uint64_t obj_size, int backend, int checksum,
+                       uint32_t payload_crc, int legacy, uint8_t out[80]);
+
 /* xor_hd_fragments_needed (xor_hd_code.c:209-412); needed ends with -1. */
 int ecamd_xor_fragments_needed(int k, int m, int hd, const unsigned int *parity_bms,
                                const unsigned int *data_bms, const int *to_reconstruct,

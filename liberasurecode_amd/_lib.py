@@ -74,6 +74,8 @@ def host():
         _proto(h, "ecamd_xor_check_plan_degraded", C.c_int,
                [C.c_int, C.c_int, C.c_int, IP, C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(C.c_uint)])
         _proto(h, "ecamd_xor_decode_masks_plan", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int])
+        _proto(h, "ecamd_frame_header", C.c_int,
+               [C.c_int, C.c_uint32, C.c_uint64, C.c_int, C.c_int, C.c_uint32, C.c_int, C.c_void_p])
         _host = h
     return _host
 
@@ -191,6 +193,10 @@ def dev():
         _proto(d, "ecamd_xor_decode_masks", C.c_int,
                [C.c_int, C.c_int, C.c_int, VP, C.c_int, VP, C.c_int64, C.c_int64, C.c_int64, C.c_int, VP, VP, VP])
         _proto(d, "ecamd_xor_decode_masks_launches", C.c_longlong, [])
+        _proto(d, "ecamd_frame_reconstruct_masks", C.c_int,
+               [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, VP, VP, C.c_int64, C.c_int64, C.c_uint64, C.c_int, VP, VP,
+                VP])
+        _proto(d, "ecamd_frame_reconstruct_masks_launches", C.c_longlong, [])
         _proto(d, "ecamd_percall_reset", None, [])
         _proto(d, "ecamd_percall_status", C.c_int, [])
         _proto(d, "ecamd_fault_inject", C.c_int, [C.c_char_p, C.c_int])

@@ -25,14 +25,11 @@
 #include <type_traits>
 
 #include "ecamd_crc_dev.hpp"
+#include "ecamd_crc_span.hpp"
 #include "ecamd_frame.hpp"
 #include "ecamd_isa.hpp"
 
 namespace ecamd {
-
-using crcdev::lmap;
-using crcdev::piece_r0;
-using crcdev::piece_words;
 
 namespace {
 
@@ -41,13 +38,6 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ u32x4 nt_load16(const uint8_t* p)
 {
     return __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p));
-}
-
-__device__ __forceinline__ uint32_t byte_step(const uint32_t* T, uint32_t s, uint32_t b, int legacy)
-{
-    uint32_t sh = s >> 8;
-    if (legacy && (s & 0x80000000u)) sh |= 0xff000000u;
-    return T[(s ^ b) & 0xffu] ^ sh;
 }
 
 __device__ __forceinline__ const uint8_t* item_ptr(const CrcArgs& a, int64_t item)
@@ -59,79 +49,23 @@ __device__ __forceinline__ const uint8_t* item_ptr(const CrcArgs& a, int64_t ite
 
 }  // namespace
 
-// lane l takes lane l + N of its row of 16 (DPP row_shl; past the row's end: 0)
-template <int N>
-__device__ __forceinline__ uint32_t row_shl(uint32_t x)
-{
-    return static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(x), 0x100 + N, 0xf, 0xf, false));
-}
-
 template <int MB, int G, bool POS>
 __global__ __launch_bounds__(512) void crc_partial_kernel(const CrcArgs a, const uint32_t* __restrict__ img,
                                                           uint32_t* __restrict__ partial)
 {
-    // POS: position tables -- piece u of a group of 4 has its own tables with the shift to the
-    // group's last piece (A^(1024*(3-u))) folded in, so the lane state takes one A^4096 step per
-    // 4 pieces instead of four A^1024 steps (a quarter of the serial lookup chain).
-    constexpr int PW = piece_words(MB), PIECE = POS ? 4 * PW : PW;
-    constexpr int FIELDS = (32 / G) << G, WORDS = PIECE + 7 * FIELDS;
+    constexpr int WORDS = crcdev::SpanTables<MB, G, POS>::WORDS;
     __shared__ uint32_t tab[WORDS];
     for (int i = threadIdx.x; i < WORDS; i += blockDim.x) tab[i] = img[i];
     __syncthreads();
-    const uint32_t* gap = tab + PIECE;
     const int lane = threadIdx.x & 63;
     const int nw = blockDim.x >> 6;
     const int64_t total = static_cast<int64_t>(a.items) * a.nspans;
-    const int64_t span = static_cast<int64_t>(a.J) * 1024;
     for (int64_t ws = static_cast<int64_t>(blockIdx.x) * nw + (threadIdx.x >> 6); ws < total;
          ws += static_cast<int64_t>(gridDim.x) * nw) {
         const int64_t item = ws / a.nspans;
         const int q = static_cast<int>(ws - item * a.nspans);
         const uint8_t* p = item_ptr(a, item) + a.payload_off;
-        const int64_t start = a.body - static_cast<int64_t>(a.nspans - q) * span + lane * 16;
-        uint32_t st = 0;
-        // Two groups of 4 pieces in flight: group g+1 is loading while group g is looked up.  The
-        // loads are unconditional buffer loads: a piece before the payload (the first span's
-        // leading zeros) or past the span gets an out-of-range offset, which reads zeros with no
-        // memory traffic, so the compiler can count the loads in flight (vmcnt(N), not vmcnt(0)).
-        const auto rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(p), 0,
-                                                          static_cast<int>(a.body), 0x00020000);
-        auto load4 = [&](int j, u32x4 (&v)[4]) {
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int64_t off = start + static_cast<int64_t>(j + u) * 1024;
-                const bool live = j + u < a.J && off >= 0;
-                v[u] = __builtin_amdgcn_raw_buffer_load_b128(rs, live ? static_cast<int>(off)
-                                                                      : static_cast<int>(0x80000000u),
-                                                             0, 2);
-            }
-        };
-        u32x4 cur[4], nxt[4];
-        load4(0, cur);
-        for (int j = 0; j < a.J; j += 4) {
-            load4(j + 4, nxt);
-            if constexpr (POS) {
-                st = xor3(lmap<G>(gap, st), piece_r0<MB>(tab, cur[0]), piece_r0<MB>(tab + PW, cur[1])) ^
-                     piece_r0<MB>(tab + 2 * PW, cur[2]) ^ piece_r0<MB>(tab + 3 * PW, cur[3]);
-            } else {
-#pragma unroll
-                for (int u = 0; u < 4; ++u) st = lmap<G>(gap, st) ^ piece_r0<MB>(tab, cur[u]);
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) cur[u] = nxt[u];
-        }
-        // Lane l's state sits (63 - l) pieces before the span end: fold pairs, quads, ... -- inside
-        // each row of 16 lanes by DPP row_shl (lane l takes lane l + 2^t; only the lanes that are
-        // multiples of 2^(t+1) matter), then the 4 row values by v_readlane, folded on uniform values
-        // (no ds_bpermute: the LDS serves the lookups; broadcast lookups do not conflict)
-        st = lmap<G>(tab + PIECE + FIELDS * 1, st) ^ row_shl<1>(st);
-        st = lmap<G>(tab + PIECE + FIELDS * 2, st) ^ row_shl<2>(st);
-        st = lmap<G>(tab + PIECE + FIELDS * 3, st) ^ row_shl<4>(st);
-        st = lmap<G>(tab + PIECE + FIELDS * 4, st) ^ row_shl<8>(st);
-        const uint32_t r0 = __builtin_amdgcn_readlane(st, 0), r1 = __builtin_amdgcn_readlane(st, 16);
-        const uint32_t r2 = __builtin_amdgcn_readlane(st, 32), r3 = __builtin_amdgcn_readlane(st, 48);
-        const uint32_t s0 = lmap<G>(tab + PIECE + FIELDS * 5, r0) ^ r1, s1 = lmap<G>(tab + PIECE + FIELDS * 5, r2) ^ r3;
-        st = lmap<G>(tab + PIECE + FIELDS * 6, s0) ^ s1;
+        const uint32_t st = crcdev::span_r0<MB, G, POS>(a, tab, p, q, lane);  // (ecamd_crc_span.hpp)
         if (lane == 0) partial[ws] = st;
     }
 }
@@ -145,53 +79,16 @@ ECAMD_CRC_INST(4, 8, true) ECAMD_CRC_INST(0, 8, true) ECAMD_CRC_INST(1, 8, true)
 ECAMD_CRC_INST(2, 8, true) ECAMD_CRC_INST(3, 8, true)
 #undef ECAMD_CRC_INST
 
-namespace {
-
-template <int N>
-__device__ __forceinline__ void put(uint8_t* h, int off, uint64_t v)
-{
-#pragma unroll
-    for (int i = 0; i < N; ++i) h[off + i] = static_cast<uint8_t>(v >> (8 * i));
-}
-
-template <int N>
-__device__ __forceinline__ uint32_t get(const uint8_t* h, int off)
-{
-    uint32_t v = 0;
-#pragma unroll
-    for (int i = 0; i < N; ++i) v |= static_cast<uint32_t>(h[off + i]) << (8 * i);
-    return v;
-}
-
-__device__ __forceinline__ uint32_t meta_crc(const uint32_t* T, const uint8_t* h, int legacy)
-{
-    uint32_t s = ~0u;
-#pragma unroll
-    for (int i = 0; i < kMetaBytes; ++i) s = byte_step(T, s, h[i], legacy);
-    return ~s;
-}
-
-}  // namespace
-
 __global__ void crc_finalize_kernel(const CrcArgs a, const uint32_t* __restrict__ img,
                                     const uint32_t* __restrict__ partial, uint32_t* __restrict__ crc_out,
                                     const HeaderArgs h)
 {
     const int64_t item = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
     if (item >= a.items) return;
-    const uint32_t* span = img + a.span_off;
-    const uint32_t* T = img + a.t_off;
     const uint8_t* frag = item_ptr(a, item);
     uint32_t crc = 0;
     if (a.nspans > 0) {
-        uint32_t acc = 0;
-        const uint32_t* pp = partial + item * a.nspans;
-        for (int q = 0; q < a.nspans; ++q) {
-            acc = span[acc & 0xff] ^ span[256 + ((acc >> 8) & 0xff)] ^
-                  span[512 + ((acc >> 16) & 0xff)] ^ span[768 + (acc >> 24)] ^ pp[q];
-        }
-        const uint8_t* p = frag + a.payload_off;
-        for (int64_t i = a.body; i < a.len; ++i) acc = byte_step(T, acc, p[i], a.legacy);
+        uint32_t acc = crcdev::payload_r0(a, img, partial + item * a.nspans, frag + a.payload_off);
         if (a.tail_crc) {
             uint32_t sh = 0;
 #pragma unroll
@@ -202,30 +99,11 @@ __global__ void crc_finalize_kernel(const CrcArgs a, const uint32_t* __restrict_
         if (crc_out) crc_out[item] = crc;
     }
     if (!h.write) return;
-    // add_fragment_metadata (src/erasurecode_postprocessing.c:37-69) on a zeroed header
-    // (alloc_fragment_buffer, src/erasurecode_helpers.c:124-138).
-    uint8_t hd[kHeaderBytes];
-#pragma unroll
-    for (int i = 0; i < kHeaderBytes; ++i) hd[i] = 0;
+    // the header's text: ecamd_frame_header.hpp
+    uint32_t hd[kHeaderWords];
     const int f = static_cast<int>(item % a.nfrag);
-    put<4>(hd, 0, static_cast<uint32_t>(h.idx0 + f));
-    put<4>(hd, 4, h.size);
-    put<4>(hd, 8, h.backend_meta_size);
-    put<8>(hd, 12, h.orig_data_size);
-    put<1>(hd, 20, h.chksum_type);
-    if (h.chksum_type == kChksumCrc32) put<4>(hd, 21, crc);
-    put<1>(hd, 54, h.backend_id);
-    put<4>(hd, 55, h.backend_version);
-    put<4>(hd, 59, kFragMagic);
-    put<4>(hd, 63, h.libec_version);
-    put<4>(hd, 67, meta_crc(T, hd, a.legacy));
-    uint8_t* out = const_cast<uint8_t*>(frag);
-#pragma unroll
-    for (int c = 0; c < kHeaderBytes / 16; ++c) {
-        uint4 v = make_uint4(get<4>(hd, 16 * c), get<4>(hd, 16 * c + 4), get<4>(hd, 16 * c + 8),
-                             get<4>(hd, 16 * c + 12));
-        *reinterpret_cast<uint4*>(out + 16 * c) = v;
-    }
+    frame_header_fill(hd, h, static_cast<uint32_t>(h.idx0 + f), crc, img + a.t_off, a.legacy);
+    crcdev::store_header(const_cast<uint8_t*>(frag), hd);
 }
 
 __global__ void crc_combine_kernel(const uint32_t* __restrict__ tiles, uint32_t* __restrict__ out,
@@ -547,23 +425,23 @@ __global__ void frame_verify_kernel(const CrcArgs a, const uint32_t* __restrict_
     const int64_t item = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
     if (item >= a.items) return;
     const uint8_t* frag = item_ptr(a, item);
-    uint8_t hd[kHeaderBytes];
+    uint32_t hd[kHeaderWords];
 #pragma unroll
-    for (int c = 0; c < kHeaderBytes / 16; ++c) {
-        uint4 v = *reinterpret_cast<const uint4*>(frag + 16 * c);
-        put<4>(hd, 16 * c, v.x);
-        put<4>(hd, 16 * c + 4, v.y);
-        put<4>(hd, 16 * c + 8, v.z);
-        put<4>(hd, 16 * c + 12, v.w);
+    for (int c = 0; c < kHeaderWords / 4; ++c) {
+        const uint4 v = *reinterpret_cast<const uint4*>(frag + 16 * c);
+        hd[4 * c] = v.x;
+        hd[4 * c + 1] = v.y;
+        hd[4 * c + 2] = v.z;
+        hd[4 * c + 3] = v.w;
     }
     uint32_t st = 0;
-    if (get<4>(hd, 59) != kFragMagic) st |= 1u;
-    const uint32_t stored = get<4>(hd, 67);
-    if (stored != meta_crc(img_zlib + a.t_off, hd, 0) && stored != meta_crc(img_legacy + a.t_off, hd, 1))
+    if (frame_get32(hd, kHdrMagic) != kFragMagic) st |= 1u;
+    const uint32_t stored = frame_get32(hd, kHdrMetaChksum);
+    if (stored != frame_meta_crc(img_zlib + a.t_off, hd, 0) && stored != frame_meta_crc(img_legacy + a.t_off, hd, 1))
         st |= 2u;
-    if (get<4>(hd, 0) != static_cast<uint32_t>(item % a.nfrag)) st |= 4u;
-    if (get<4>(hd, 4) != static_cast<uint32_t>(bs)) st |= 8u;
-    if (hd[20] == kChksumCrc32 && crc && get<4>(hd, 21) != crc[item]) st |= 16u;
+    if (frame_get32(hd, kHdrIdx) != static_cast<uint32_t>(item % a.nfrag)) st |= 4u;
+    if (frame_get32(hd, kHdrSize) != static_cast<uint32_t>(bs)) st |= 8u;
+    if (frame_byte(hd, kHdrChksumType) == kChksumCrc32 && crc && frame_get32(hd, kHdrChksum) != crc[item]) st |= 16u;
     status[item] = st;
 }
 

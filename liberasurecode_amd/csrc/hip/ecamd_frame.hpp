@@ -3,12 +3,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-namespace ecamd {
+#include <type_traits>
 
-constexpr int kHeaderBytes = 80;           // sizeof(fragment_header_t), include/erasurecode.h
-constexpr int kMetaBytes = 59;             // sizeof(fragment_metadata_t)
-constexpr uint32_t kFragMagic = 0xb0c5ecc;  // LIBERASURECODE_FRAG_HEADER_MAGIC
-constexpr uint8_t kChksumCrc32 = 2;        // CHKSUM_CRC32
+#include "ecamd_frame_header.hpp"  // the header's layout, HeaderArgs
+
+namespace ecamd {
 
 // Items = nstripes * nfrag payloads; item (s, f) fragment at base + s*stripe_stride + f*frag_stride,
 // its payload at + payload_off, len bytes (body = len & ~15 handled by the partial kernel).
@@ -34,18 +33,6 @@ struct CrcArgs {
     const uint32_t* tail_crc;
     uint32_t tail_c0;
     uint32_t tail_cols[32];
-};
-
-struct HeaderArgs {
-    int write;
-    int idx0;
-    uint32_t size;
-    uint32_t backend_meta_size;
-    uint64_t orig_data_size;
-    uint32_t backend_version;
-    uint32_t libec_version;
-    uint8_t chksum_type;
-    uint8_t backend_id;
 };
 
 struct SplitArgs {
@@ -107,5 +94,50 @@ __global__ void frame_verify_kernel(const CrcArgs a, const uint32_t* __restrict_
                                     const uint32_t* __restrict__ img_legacy,
                                     const uint32_t* __restrict__ crc, int64_t bs,
                                     uint32_t* __restrict__ status);
+
+// Which instantiation of the span kernels a call takes, from the knobs: B = crc_bits (4..8: MB = B - 4
+// byte-table dwords per piece), G the gap field bits (4 only with B == 4), pos the position tables
+// (only with G == 8).  f(MB, G, POS) as integral constants: the one place the three pick a kernel.
+struct CrcForm {
+    int B, G;
+    bool pos;
+};
+template <class F>
+void with_crc_form(const CrcForm& c, F&& f)
+{
+    using std::integral_constant;
+    auto by_bits = [&](auto g, auto p) {
+        switch (c.B) {
+        case 8: f(integral_constant<int, 4>{}, g, p); break;
+        case 7: f(integral_constant<int, 3>{}, g, p); break;
+        case 6: f(integral_constant<int, 2>{}, g, p); break;
+        case 5: f(integral_constant<int, 1>{}, g, p); break;
+        default: f(integral_constant<int, 0>{}, g, p); break;
+        }
+    };
+    if (c.pos)
+        by_bits(integral_constant<int, 8>{}, std::true_type{});
+    else if (c.G == 4)
+        f(integral_constant<int, 0>{}, integral_constant<int, 4>{}, std::false_type{});
+    else
+        by_bits(integral_constant<int, 8>{}, std::false_type{});
+}
+
+// ---- ecamd_frame_masks.hip: the stamp stage of ecamd_frame_reconstruct_masks ----
+// Items (stripe s, j < jmax, span q): item j of stripe s is the j-th fragment of lost[s] when result[s]
+// says the stripe was rebuilt (frame_masks_target, ecamd_frame_header.hpp), and nothing otherwise.
+struct StampArgs {
+    const uint32_t* lost;    // one mask word per stripe
+    const uint32_t* result;  // the payload decode's result word per stripe
+    int nstripes;
+    int jmax;
+};
+// On `stream`, behind the payload decode: with a.nspans > 0, crc_partial_masks_kernel<form> (grid
+// workgroups of 512) writes r0 of span q of item (s, j) to partial[(s*jmax + j)*a.nspans + q]; then
+// frame_stamp_masks_kernel, one thread per (s, j), folds them with the payload's tail bytes and writes
+// the fragment's 80 header bytes.  `a` as run_crc fills it for the fragments at a.base (a.items unused),
+// d_img its image.
+int frame_stamp_masks(const CrcArgs& a, const CrcForm& form, const uint32_t* d_img, const StampArgs& sa, uint32_t* partial,
+                      const HeaderArgs& h, unsigned grid, void* stream);
 
 }  // namespace ecamd

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cstdlib>
 #include <map>
 #include <memory>
@@ -18,6 +19,7 @@
 #include "ecamd_host.h"
 #include "ecamd_internal.hpp"
 #include "ecamd_kernels.hpp"
+#include "ecamd_masks_plan.hpp"
 
 using namespace ecamd;
 
@@ -25,8 +27,6 @@ namespace {
 
 constexpr int kBackendXor = 3;   // EC_BACKEND_FLAT_XOR_HD
 constexpr int kBackendRs = 6;    // EC_BACKEND_LIBERASURECODE_RS_VAND
-constexpr uint32_t kLibecVersion = (1u << 16) | (8u << 8);  // LIBERASURECODE_VERSION 1.8.0
-constexpr uint32_t kBackendVersion = 1u << 16;              // ec_backend_version 1.0.0
 
 // LIBERASURECODE_WRITE_LEGACY_CRC, read per call as the reference does
 // (src/erasurecode_postprocessing.c:59-60, src/erasurecode_helpers.c:479-480).
@@ -42,6 +42,7 @@ struct DevImage {
 };
 
 std::mutex g_mu;
+std::atomic<long long> g_reconstruct_masks_launches{0};  // stamp-kernel launches
 std::map<std::tuple<int, int, int, int, int, int>, std::unique_ptr<DevImage>> g_images;  // dev, legacy, B, J, G, pos
 
 int image(int dev, bool legacy, int B, int J, int G, bool pos, const DevImage** out)
@@ -130,6 +131,57 @@ int check_frames(const void* frags, int64_t stripe_stride, int64_t frag_stride, 
     return 0;
 }
 
+// How a CRC pass over payloads of `len` bytes runs under the current knobs: the form of the span
+// kernel, its image, and the length-dependent part of CrcArgs (len, body, J, nspans -- 0 without
+// with_crc: headers only --, c0, the image's offsets, legacy).  The one owner of the knobs crc_bits,
+// crc_gap_bits, crc_pos and crc_span_kib.
+struct CrcPlan {
+    CrcForm form;
+    const DevImage* di = nullptr;
+    CrcArgs a{};
+};
+int crc_plan(int dev, bool legacy, bool with_crc, int64_t len, CrcPlan* out)
+{
+    const int B = g_tune.crc_bits;  // 4 .. 8 (host/crc.cpp build_crc_image)
+    const int G = B != 4 ? 8 : (g_tune.crc_gap_bits == 4 ? 4 : 8);
+    const bool pos = g_tune.crc_pos != 0 && G == 8;
+    const int64_t body = len & ~int64_t(15);
+    const int span_knob = g_tune.crc_span_kib;
+    const int jmax = span_knob > 0 ? span_knob : 16;  // KiB per span
+    int J = static_cast<int>(std::min<int64_t>(jmax, std::max<int64_t>(4, ((body / 1024 + 3) / 4) * 4)));
+    out->form = CrcForm{B, G, pos};
+    const int rc = image(dev, legacy, B, J, G, pos, &out->di);
+    if (rc) return rc;
+    CrcArgs& a = out->a;
+    a = CrcArgs{};
+    a.len = len;
+    a.body = body;
+    a.J = J;
+    a.legacy = legacy ? 1 : 0;
+    a.span_off = static_cast<uint32_t>(out->di->img.span_off);
+    a.t_off = static_cast<uint32_t>(out->di->img.t_off);
+    a.nspans = 0;
+    if (with_crc) {
+        const int64_t span = static_cast<int64_t>(J) * 1024;
+        a.nspans = static_cast<int>(std::max<int64_t>(1, (body + span - 1) / span));
+        a.c0 = zero_shift(CrcMachine(legacy), static_cast<uint64_t>(len)).apply(~0u);
+    }
+    return 0;
+}
+
+// Workgroups (8 waves each) of a span kernel over `waves` spans.
+unsigned crc_grid(int dev, int B, int64_t waves)
+{
+    int wpc = g_tune.crc_wgs;
+    // Measured on MI355X (C3 payloads, 3.5 GiB): B=8 at 2 workgroups/CU 6.35 TB/s, 3: 5.94,
+    // 4 (LDS-capped to 3): 5.95; B=4 at 4: 5.36 ("Framing"); the default B=5 with
+    // position tables at 8 (twice the resident grid): 0.703 -> 0.724 of 8 TB/s against 4
+    // (tools/crc_grid_sweep.py, profiles/r03_crc_grid_sweep.log)
+    if (wpc <= 0) wpc = B == 8 ? 2 : 8;
+    return static_cast<unsigned>(
+        std::max<int64_t>(1, std::min<int64_t>(static_cast<int64_t>(dev_cu_count(dev)) * wpc, (waves + 7) / 8)));
+}
+
 // CRC32 of nfrag payloads per stripe (fragment f at base + s*ss + f*fs, payload at +payload_off)
 // and, if h.write, the headers.  crc_out may be null.
 int run_crc(int dev, bool legacy, bool with_crc, const uint8_t* base, int64_t ss, int64_t fs,
@@ -138,74 +190,28 @@ int run_crc(int dev, bool legacy, bool with_crc, const uint8_t* base, int64_t ss
 {
     const int64_t items = static_cast<int64_t>(nfrag) * nstripes;
     if (items == 0) return 0;
-    const int B = g_tune.crc_bits;  // 4 .. 8 (host/crc.cpp build_crc_image)
-    const int G = B != 4 ? 8 : (g_tune.crc_gap_bits == 4 ? 4 : 8);
-    const bool pos = g_tune.crc_pos != 0 && G == 8;
-    const int64_t body = len & ~int64_t(15);
-    const int span_knob = g_tune.crc_span_kib;
-    const int jmax = span_knob > 0 ? span_knob : 16;  // KiB per span
-    int J = static_cast<int>(std::min<int64_t>(jmax, std::max<int64_t>(4, ((body / 1024 + 3) / 4) * 4)));
-    const DevImage* di = nullptr;
-    int rc = image(dev, legacy, B, J, G, pos, &di);
+    CrcPlan plan;
+    int rc = crc_plan(dev, legacy, with_crc, len, &plan);
     if (rc) return rc;
-    CrcArgs a{};
+    const DevImage* di = plan.di;
+    CrcArgs& a = plan.a;
     a.base = base;
     a.stripe_stride = ss;
     a.frag_stride = fs;
     a.payload_off = payload_off;
-    a.len = len;
-    a.body = body;
     a.items = items;
     a.nfrag = nfrag;
-    a.J = J;
-    a.legacy = legacy ? 1 : 0;
-    a.span_off = static_cast<uint32_t>(di->img.span_off);
-    a.t_off = static_cast<uint32_t>(di->img.t_off);
-    a.nspans = 0;
     hipStream_t st = static_cast<hipStream_t>(stream);
     uint32_t* partial = nullptr;
     if (with_crc) {
-        const int64_t span = static_cast<int64_t>(J) * 1024;
-        a.nspans = static_cast<int>(std::max<int64_t>(1, (body + span - 1) / span));
-        a.c0 = zero_shift(CrcMachine(legacy), static_cast<uint64_t>(len)).apply(~0u);
         const int64_t waves = items * a.nspans;
         rc = stream_scratch(dev, stream, 0, static_cast<size_t>(waves), &partial);  // span partials
         if (rc) return rc;
-        int wpc = g_tune.crc_wgs;
-        // Measured on MI355X (C3 payloads, 3.5 GiB): B=8 at 2 workgroups/CU 6.35 TB/s, 3: 5.94,
-        // 4 (LDS-capped to 3): 5.95; B=4 at 4: 5.36 ("Framing"); the default B=5 with
-        // position tables at 8 (twice the resident grid): 0.703 -> 0.724 of 8 TB/s against 4
-        // (tools/crc_grid_sweep.py, profiles/r03_crc_grid_sweep.log)
-        if (wpc <= 0) wpc = B == 8 ? 2 : 8;
-        const int64_t grid = std::max<int64_t>(1, std::min<int64_t>(
-                                                      static_cast<int64_t>(dev_cu_count(dev)) * wpc,
-                                                      (waves + 7) / 8));
-        const dim3 gd(static_cast<unsigned>(grid)), bd(512);
-        // template: number of byte-table dwords per piece, gap field bits, position tables
-#define ECAMD_CRC_LAUNCH(MB, GG, P) \
-    hipLaunchKernelGGL((crc_partial_kernel<MB, GG, P>), gd, bd, 0, st, a, di->d, partial)
-        if (pos) {
-            switch (B) {
-            case 8: ECAMD_CRC_LAUNCH(4, 8, true); break;
-            case 7: ECAMD_CRC_LAUNCH(3, 8, true); break;
-            case 6: ECAMD_CRC_LAUNCH(2, 8, true); break;
-            case 5: ECAMD_CRC_LAUNCH(1, 8, true); break;
-            default: ECAMD_CRC_LAUNCH(0, 8, true); break;
-            }
-        } else {
-            switch (B) {
-            case 8: ECAMD_CRC_LAUNCH(4, 8, false); break;
-            case 7: ECAMD_CRC_LAUNCH(3, 8, false); break;
-            case 6: ECAMD_CRC_LAUNCH(2, 8, false); break;
-            case 5: ECAMD_CRC_LAUNCH(1, 8, false); break;
-            default:
-                if (G == 8)
-                    ECAMD_CRC_LAUNCH(0, 8, false);
-                else
-                    ECAMD_CRC_LAUNCH(0, 4, false);
-            }
-        }
-#undef ECAMD_CRC_LAUNCH
+        const dim3 gd(crc_grid(dev, plan.form.B, waves)), bd(512);
+        with_crc_form(plan.form, [&](auto mb, auto g, auto p) {
+            hipLaunchKernelGGL((crc_partial_kernel<decltype(mb)::value, decltype(g)::value, decltype(p)::value>), gd, bd, 0,
+                               st, a, di->d, partial);
+        });
         HIP_TRY(hipGetLastError());
     }
     if (with_crc || h.write) {
@@ -218,17 +224,7 @@ int run_crc(int dev, bool legacy, bool with_crc, const uint8_t* base, int64_t ss
 
 HeaderArgs header_args(const Code& c, int checksum, int64_t bs, uint64_t obj_size, int idx0)
 {
-    HeaderArgs h{};
-    h.write = 1;
-    h.idx0 = idx0;
-    h.size = static_cast<uint32_t>(bs);
-    h.backend_meta_size = 0;  // get_backend_metadata_size is 0 for both backends
-    h.orig_data_size = obj_size;
-    h.backend_version = kBackendVersion;
-    h.libec_version = kLibecVersion;
-    h.chksum_type = static_cast<uint8_t>(checksum);
-    h.backend_id = static_cast<uint8_t>(c.backend);
-    return h;
+    return frame_header_args(c.backend, checksum, bs, obj_size, idx0);
 }
 
 int grid_for(int dev, int64_t work)
@@ -1098,6 +1094,61 @@ int ecamd_frame_reconstruct(int backend, int k, int m, int hd, int checksum, con
                    stripe_stride, frag_stride, kHeaderBytes, 1, bs, nstripes, nullptr,
                    header_args(c, checksum, bs, obj_size, dest), stream);
 }
+
+// The payload decode from device masks, then the stamp stage (hip/ecamd_frame_masks.hip) over the
+// fragments the decode's result words say were rebuilt.
+int ecamd_frame_reconstruct_masks(int backend, int k, int m, int hd, int checksum, const uint32_t* d_lost,
+                                  void* d_frags, int64_t stripe_stride, int64_t frag_stride, uint64_t obj_size,
+                                  int nstripes, uint32_t* d_result, uint32_t* d_counts, void* stream)
+{
+    int dev = 0;
+    int rc = dev_ensure(&dev);
+    if (rc) return rc;
+    const StreamUse use(dev, stream);  // its stream context outlives this call
+    const Code c = make_code(backend, k, m, hd);
+    if ((rc = check_code(c))) return rc;
+    if (backend == kBackendRs && m > kMasksMaxOut)
+        return dev_fail(ECAMD_EINVAL, "reconstruct_masks: rs_vand needs m <= %d (m=%d)", kMasksMaxOut, m);
+    const int64_t bs = blocksize_of(c, obj_size);
+    if ((rc = check_frames(d_frags, stripe_stride, frag_stride, bs, k + m, nstripes))) return rc;
+    if (!d_lost) return dev_fail(ECAMD_EINVAL, "null masks");
+    if (nstripes == 0) return 0;
+    // the most fragments a rebuilt stripe has lost: the stamp stage's items per stripe
+    const int jmax = backend == kBackendRs ? std::min(m, kMasksMaxOut) : hd - 1;
+    CrcPlan plan;
+    if ((rc = crc_plan(dev, legacy_crc(), checksum == kChksumCrc32, bs, &plan))) return rc;
+    // The stamp stage decides what to stamp from the decode's result words: library scratch when the
+    // caller does not want them.  Both scratch slots before anything is enqueued.
+    uint32_t *result = d_result, *partial = nullptr;
+    if (!result && (rc = stream_scratch(dev, stream, kFrameMasksResultSlot, static_cast<size_t>(nstripes), &result))) return rc;
+    const int64_t waves = static_cast<int64_t>(nstripes) * jmax * plan.a.nspans;
+    if (waves && (rc = stream_scratch(dev, stream, kFrameMasksPartialSlot, static_cast<size_t>(waves), &partial))) return rc;
+    auto* frags = static_cast<uint8_t*>(d_frags);
+    if (backend == kBackendRs)
+        rc = ecamd_rs_decode_masks(k, m, d_lost, 1, frags + kHeaderBytes, stripe_stride, frag_stride, bs, nstripes, result,
+                                   d_counts, stream);
+    else
+        rc = ecamd_xor_decode_masks(k, m, hd, d_lost, 1, frags + kHeaderBytes, stripe_stride, frag_stride, bs, nstripes,
+                                    result, d_counts, stream);
+    if (rc) return rc;
+    CrcArgs& a = plan.a;
+    a.base = frags;
+    a.stripe_stride = stripe_stride;
+    a.frag_stride = frag_stride;
+    a.payload_off = kHeaderBytes;
+    a.nfrag = k + m;
+    const StampArgs sa{d_lost, result, nstripes, jmax};
+    // knob pairs_grid > 0 caps the masked span kernel's grid as it caps the decode's (tests: grid-stride)
+    unsigned grid = crc_grid(dev, plan.form.B, waves);
+    if (g_tune.pairs_grid > 0) grid = std::min(grid, static_cast<unsigned>(g_tune.pairs_grid));
+    if ((rc = frame_stamp_masks(a, plan.form, plan.di->d, sa, partial, header_args(c, checksum, bs, obj_size, 0), grid,
+                                stream)))
+        return rc;
+    g_reconstruct_masks_launches.fetch_add(1, std::memory_order_relaxed);
+    return 0;
+}
+
+long long ecamd_frame_reconstruct_masks_launches(void) { return g_reconstruct_masks_launches.load(std::memory_order_relaxed); }
 
 int ecamd_frame_verify(int nfrag, int64_t blocksize, int legacy, const void* d_frags,
                        int64_t stripe_stride, int64_t frag_stride, int nstripes,

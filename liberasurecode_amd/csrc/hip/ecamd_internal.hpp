@@ -154,11 +154,16 @@ int side_join(int dev, void* stream);
 // zeroed when it is (re)allocated.  Slot 5: the fragments the checks and locates of ecamd_check.hip
 // compute to compare the stored ones against (generic stage; at most kCheckScratchBytes).  Slot 6: the
 // per-stripe records of ecamd_rs_decode_masks (ecamd_decode_masks.hip; 560 bytes per stripe of the
-// largest batch seen).
-constexpr int kStreamScratchSlots = 7;
+// largest batch seen).  Slots 7 and 8: ecamd_frame_reconstruct_masks (ecamd_frame_api.hip) -- the decode's
+// result words when the caller passes none, and the span partials of its stamp stage; slots of their
+// own, so that neither the decode's records (6), a check's fragments (5) nor a CRC pass's partials (0)
+// enqueued around it on the same stream share a buffer with them.
+constexpr int kStreamScratchSlots = 9;
 constexpr int kSmallCrcScratchSlot = 4;
 constexpr int kCheckScratchSlot = 5;
 constexpr int kMasksPlanScratchSlot = 6;
+constexpr int kFrameMasksResultSlot = 7;
+constexpr int kFrameMasksPartialSlot = 8;
 constexpr size_t kCheckScratchBytes = size_t(64) << 20;
 int stream_scratch(int dev, void* stream, int slot, size_t words, uint32_t** out);
 // A framed call in progress on (dev, stream): its context is not released until the call has

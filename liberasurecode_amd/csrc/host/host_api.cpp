@@ -7,6 +7,8 @@
 #include <vector>
 
 #include "bitslice.hpp"
+#include "crc.hpp"
+#include "ecamd_frame_header.hpp"
 #include "ecamd_xor_masks_plan.hpp"
 #include "gf16.hpp"
 #include "tables.hpp"
@@ -303,6 +305,18 @@ int ecamd_xor_decode_masks_plan(int k, int m, int hd, void* table, int capacity)
         }
     }
     return count;
+}
+
+int ecamd_frame_header(int idx, uint32_t blocksize, uint64_t obj_size, int backend, int checksum, uint32_t payload_crc,
+                       int legacy, uint8_t out[80])
+{
+    if (!out || idx < 0) return -1;
+    const CrcMachine mach(legacy != 0);
+    uint32_t w[kHeaderWords];
+    frame_header_fill(w, frame_header_args(backend, checksum, blocksize, obj_size, 0), static_cast<uint32_t>(idx), payload_crc,
+                      mach.t, legacy ? 1 : 0);
+    for (int i = 0; i < kHeaderBytes; i++) out[i] = static_cast<uint8_t>(frame_byte(w, i));
+    return 0;
 }
 
 int ecamd_xor_fragments_needed(int k, int m, int hd, const unsigned int* parity_bms,

@@ -83,6 +83,74 @@ class FrameBatch:
         return (st.download(4 * n).view(np.uint32).reshape(shape),
                 crc.download(4 * n).view(np.uint32).reshape(shape))
 
+    def _reconstruct_masks(self, d_lost, d_result, d_counts, stream):
+        check(dev().ecamd_frame_reconstruct_masks(self.backend, self.k, self.m, self.hd, self.checksum, d_lost,
+                                                  self.base, self.stripe_stride, self.frag_stride,
+                                                  self.obj_size, self.nstripes, d_result, d_counts,
+                                                  _s(stream)), "frame_reconstruct_masks")
+
+    @staticmethod
+    def _wait(stream):
+        if stream is not None:
+            stream.synchronize()
+        else:
+            check(dev().ecamd_synchronize(), "synchronize")
+
+    def reconstruct_masks(self, lost_masks, stream=None):
+        """ecamd_frame_reconstruct_masks: rebuild whole -- header, checksum and payload -- the fragments each
+        stripe lost, lost_masks[s] the mask of stripe s (bit f: fragment f is lost).  lost_masks is a host
+        sequence, uploaded here, or a DeviceBuffer of nstripes uint32 the call reads in stream order.
+        Returns (result, counts) after this function's own synchronise, as device.rs_decode_masks:
+        result[s] = fragments rebuilt, 0 for an empty mask, 0x80000000 | popcount for a mask that cannot be
+        recovered (nothing of that stripe is written); counts = (left alone, rebuilt, unrecoverable)."""
+        n = max(self.nstripes, 1)
+        out = DeviceBuffer(8 * n + 16)  # result words, then the three counts
+        own = None
+        try:
+            check(dev().ecamd_memset(out.ptr, 0, 8 * n + 16), "memset")
+            if isinstance(lost_masks, DeviceBuffer):
+                d_lost = lost_masks.ptr
+            else:
+                masks = np.ascontiguousarray(np.asarray(lost_masks, dtype=np.uint32).reshape(-1))
+                if masks.size != self.nstripes:
+                    raise ValueError("one mask per stripe: %d masks, %d stripes" % (masks.size, self.nstripes))
+                own = DeviceBuffer(4 * n)
+                if self.nstripes:
+                    own.upload(masks)
+                d_lost = own.ptr
+            self._reconstruct_masks(d_lost, out.ptr, out.ptr + 4 * n, stream)
+            self._wait(stream)
+            words = out.download(8 * n + 16).view(np.uint32)
+            return words[:self.nstripes].copy(), tuple(int(c) for c in words[n:n + 3])
+        finally:
+            out.free()
+            if own is not None:
+                own.free()
+
+    def heal(self, bits=0x1F, legacy=False, stream=None):
+        """The audit-and-repair chain on one stream with one wait at the end: ecamd_frame_verify, then
+        ecamd_frame_status_masks(bits) -- by default every kind of damage the audit sees, bad or missing
+        headers included --, then ecamd_frame_reconstruct_masks on the masks, which never leave the device.
+        Returns (masks, result, counts): the mask of each stripe, and what reconstruct_masks returns."""
+        nf, n = self.k + self.m, max(self.nstripes, 1)
+        st, crc = DeviceBuffer(4 * n * nf), DeviceBuffer(4 * n * nf)
+        out = DeviceBuffer(12 * n + 16)  # masks, result words, then the three counts
+        try:
+            check(dev().ecamd_memset(out.ptr, 0, 12 * n + 16), "memset")
+            check(dev().ecamd_frame_verify(nf, self.blocksize, int(legacy), self.base, self.stripe_stride,
+                                           self.frag_stride, self.nstripes, st.ptr, crc.ptr, _s(stream)),
+                  "frame_verify")
+            check(dev().ecamd_frame_status_masks(nf, st.ptr, bits, self.nstripes, out.ptr, _s(stream)),
+                  "frame_status_masks")
+            self._reconstruct_masks(out.ptr, out.ptr + 4 * n, out.ptr + 8 * n, stream)
+            self._wait(stream)
+            words = out.download(12 * n + 16).view(np.uint32)
+            return (words[:self.nstripes].copy(), words[n:n + self.nstripes].copy(),
+                    tuple(int(c) for c in words[2 * n:2 * n + 3]))
+        finally:
+            for b in (st, crc, out):
+                b.free()
+
     def fragments(self) -> np.ndarray:
         """(S, k+m, fragment_len) uint8 host copy of the wire-format fragments."""
         raw = self.buf.download(self.nbytes)
